@@ -10,7 +10,12 @@ inputs already resident in HBM.  Payloads are independent, so N GPUs run N
 replicas on disjoint payload sets (weak scaling, no data-path collective);
 only the barrier and the max-over-ranks timing use torch.distributed.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run sets up, warms up, times the steps and prints the result line.
+--full adds what the headline figure does not need: the CPU baseline (the
+reference's C implementation on the host cores, `cpu_baseline` in the line).
+--dump-outputs DIR writes what the last timed step computed (dump_outputs).
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
        torchrun --nproc-per-node N bench.py --gpus N ...
 """
 import argparse
@@ -51,15 +56,22 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", type=int, default=3, help="BASELINE config id (workload shape)")
     ap.add_argument("--batch", type=int, default=0, help="payloads per GPU (default: the config's)")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline budget (rank 0, N=1)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs to DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: CPU baseline budget (rank 0, N=1)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline (a plain run has none)")
     ap.add_argument("--out", default="", help="also write the JSON line to this file")
     # ad-hoc shapes for DESIGN measurements (never the headline): override the config's
     ap.add_argument("--n-wanted", type=int, default=0)
     ap.add_argument("--k-wanted", type=int, default=0)
     ap.add_argument("--payload", type=int, default=0, help="payload bytes")
     ap.add_argument("--erase", type=int, default=-1, help="erasures per payload")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def partition(per_rank: int, world: int, rank: int):
@@ -181,6 +193,47 @@ def cpu_baseline(cfg, params, seconds):
                   f"{erase} erasures, {'reference cxx/RSErasureCode.c' if multi['kind'] == 'reference' else 'oracle/np_oracle.c'} "
                   f"+ crate glue (oracle/cpu_bench.c), every payload round-trip checked",
     }
+
+
+DUMP_SAMPLE = 1 << 22  # elements per sampled array: 16 MiB as float32
+DUMP_SEED = 0xD0A7
+
+
+def dump_outputs(dirname, rank, world, shards, wanted_n, out):
+    """--dump-outputs: what the last timed step left in the buffers a caller of
+    the timed path receives -- `shards` (batch x n x shard_len bytes from
+    encode_batch_dev; rows >= wanted_n are never produced and are left out) and
+    `reconstructed` (batch x out_len bytes from reconstruct_batch_dev2) -- as
+    DIR/<name>.npy (DIR/<name>_rank<r>.npy on N > 1 GPUs):
+
+    * <name>.npy: the bytes as float32; of an array above DUMP_SAMPLE elements,
+      those at DUMP_SAMPLE flat indices drawn once with a fixed seed (sorted,
+      the same for every run of the same shape);
+    * <name>_rowsum.npy: the float64 sum of the bytes of every shard (batch x
+      wanted_n; one sum per payload where there are more than DUMP_SAMPLE / 2
+      shards) and of every reconstructed payload (batch), exact below 2^53:
+      every byte of the outputs enters one of them.
+
+    The inputs are seeded by the global payload index (synth), so two builds run
+    with the same arguments can be compared file by file."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    produced = shards[:, :wanted_n, :]
+    for name, t in (("shards", produced), ("reconstructed", out)):
+        numel = t.numel()
+        if numel > DUMP_SAMPLE:
+            flat = np.sort(np.random.default_rng(DUMP_SEED).integers(0, numel, DUMP_SAMPLE, dtype=np.int64))
+            vals = t[tuple(torch.from_numpy(i).to(t.device) for i in np.unravel_index(flat, tuple(t.shape)))]
+        else:
+            vals = t.reshape(-1)
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), vals.to(torch.float32).cpu().numpy())
+        sums = t.sum(dim=-1, dtype=torch.float64)
+        if sums.numel() > DUMP_SAMPLE // 2:  # keeps the four files within 64 MB at any shape
+            sums = sums.sum(dim=-1)
+        np.save(os.path.join(dirname, f"{name}_rowsum{suffix}.npy"), sums.cpu().numpy())
 
 
 def launch_replicas(args) -> int:
@@ -329,6 +382,9 @@ def main():
     ms_step = elapsed / args.steps * 1e3
     value = aggregate_gib_s(world, batch, plen, elapsed, args.steps)
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, shards, params.wanted_n, out)
+
     kt = {name: sum(a.elapsed_time(b) for a, b in pairs) / len(pairs) for name, pairs in ev.items()}
     nshard = params.wanted_n  # == n for the BASELINE configs
     # SURVEY.md §8(d) algorithmic bytes per payload: encode = P + n * shard_len;
@@ -375,7 +431,7 @@ def main():
         "kernels": roof,
         "roundtrip_ok": ok,
     }
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         line["cpu_baseline"] = cpu_baseline(cfg, params, args.cpu_seconds)
     if rank == 0:
         s = json.dumps(line)

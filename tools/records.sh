@@ -10,8 +10,8 @@ TAG=${1:-r04}
 cd $GRAFT_REPO_ROOT
 D=gpurun_out/$TAG
 mkdir -p $D
-timeout -k 10 300 python bench.py --out $D/bench.json > $D/bench.log 2>&1 || exit $?
-for c in 2 4; do timeout -k 10 300 python bench.py --config $c --steps 10 --warmup 2 --cpu-seconds 8 --out $D/cfg$c.json > $D/cfg$c.log 2>&1 || exit $?; done
+timeout -k 10 300 python bench.py --full --out $D/bench.json > $D/bench.log 2>&1 || exit $?
+for c in 2 4; do timeout -k 10 300 python bench.py --full --config $c --steps 10 --warmup 2 --cpu-seconds 8 --out $D/cfg$c.json > $D/cfg$c.log 2>&1 || exit $?; done
 for f in bench cfg2 cfg4; do python3 -c "
 import json; d=json.load(open('$D/$f.json')); print('$f', d['value'], {k:(v['ms'], v['frac']) for k,v in d['kernels'].items()}, 'cpu', d.get('cpu_baseline', {}).get('value'))"; done
 if [ -x oracle/_ref/cpu_bench_ref ]; then exe=oracle/_ref/cpu_bench_ref; else exe=oracle/cpu_bench_port; fi
