@@ -132,6 +132,14 @@ int np_reconstruct(np_ctx* ctx, const uint8_t* const* shards, const size_t* shar
 int np_rs_reconstruct(np_ctx* ctx, const np_code_params* params, const uint8_t* const* shards,
                       const size_t* shard_lens, size_t n_received, uint8_t* out, size_t out_capacity,
                       size_t* out_len);
+/* np_restore_shards_batch_dev for one payload in host memory:
+ * shards/shard_lens/n_received as np_rs_reconstruct (same validation, same
+ * errors, odd lengths zero padded).  restored: wanted_n host pointers;
+ * restored[i] != NULL for an absent i receives 2*ceil(len/2) bytes;
+ * restored_len is the capacity of each. */
+int np_rs_restore_shards(np_ctx* ctx, const np_code_params* params, const uint8_t* const* shards,
+                         const size_t* shard_lens, size_t n_received, uint8_t* const* restored,
+                         size_t restored_len);
 /* mod.rs:247-285 ReedSolomon::reconstruct_from_systematic (first k shards, all present). */
 int np_rs_reconstruct_from_systematic(np_ctx* ctx, const np_code_params* params, const uint8_t* const* chunks,
                                       const size_t* chunk_lens, size_t n_chunks, uint8_t* out,
@@ -195,6 +203,25 @@ int np_reconstruct_codewords_batch_dev(np_ctx* ctx, const np_code_params* params
                                        size_t shard_len, size_t batch_stride, const uint8_t* d_present,
                                        size_t batch, uint8_t* d_out, size_t out_stride,
                                        np_payload_status* d_status, void* stream);
+/* Restores the missing shards in place (what the `reed-solomon-erasure` crate
+ * calls `reconstruct`, next to its payload-only `reconstruct_data`).
+ * For every payload with >= k present rows: writes each row v < wanted_n with
+ * present[b*n+v] == 0 as row v of ReedSolomon::encode(ReedSolomon::reconstruct(received))
+ * (mod.rs:117-157 after mod.rs:162-239), bit-exact for any received bytes.
+ * No other byte of d_shards is written: present rows, rows >= wanted_n, bytes
+ * between rows' end and batch_stride.  Payloads with < k present rows get
+ * NP_ERR_NEED_MORE_SHARDS in d_status and are left untouched.  Layouts and
+ * d_status (may be NULL) as np_reconstruct_batch_dev3; asynchronous on stream.
+ * k in {64, 128, 256} (every n >= 2k): the reconstruct, then an encode that
+ * stores the absent rows straight into d_shards and skips the transforms of
+ * the size-k row segments that lack none.  Every other shape (k <= 32,
+ * k >= 512): the reconstruct, the ordinary encode into context scratch, and a
+ * copy of the absent rows.  The context keeps the decoded payloads of a slice
+ * of the batch (up to 1/256 of the device's memory, 1 GiB on an MI355X; larger
+ * batches run in slices); NP_ERR_ALLOC if that scratch cannot be allocated. */
+int np_restore_shards_batch_dev(np_ctx* ctx, const np_code_params* params, uint8_t* d_shards, size_t shard_len,
+                                size_t batch_stride, const uint8_t* d_present, size_t batch,
+                                np_payload_status* d_status, void* stream);
 /* mod.rs:247-285 ReedSolomon::reconstruct_from_systematic for `batch` payloads
  * whose first k shards are all present: d_shards as for np_encode_batch_dev
  * (batch_stride >= k*shard_len, only rows 0..k-1 are read), d_out as for

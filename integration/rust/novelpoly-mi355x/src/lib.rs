@@ -203,6 +203,48 @@ impl ReedSolomon {
 		Ok(out)
 	}
 
+	/// All `wanted_n` shards of `encode(reconstruct(received_shards))`: the
+	/// received ones as given (zero padded to an even length), the absent
+	/// ones restored.  Same errors as `reconstruct`.
+	pub fn restore_shards<S: Shard>(&self, received_shards: Vec<Option<S>>) -> Result<Vec<S>> {
+		let (ptrs, lens) = shard_views(&received_shards);
+		let wanted_n = self.params.raw.wanted_n;
+		let sl = 2 * lens.iter().take(self.params.raw.n).map(|l| (l + 1) / 2).max().unwrap_or(0);
+		let mut restored: Vec<Vec<u8>> = (0..wanted_n)
+			.map(|i| if ptrs.get(i).map_or(true, |p| p.is_null()) { vec![0u8; sl.max(1)] } else { Vec::new() })
+			.collect();
+		let outs: Vec<*mut u8> =
+			restored.iter_mut().map(|r| if r.is_empty() { std::ptr::null_mut() } else { r.as_mut_ptr() }).collect();
+		check(unsafe {
+			sys::np_rs_restore_shards(
+				self.ctx.raw,
+				&self.params.raw,
+				ptrs.as_ptr(),
+				lens.as_ptr(),
+				ptrs.len(),
+				outs.as_ptr(),
+				sl,
+			)
+		})?;
+		let mut received = received_shards;
+		received.resize_with(wanted_n, || None);
+		Ok(received
+			.into_iter()
+			.zip(restored)
+			.map(|(have, mut got)| match have {
+				Some(s) => {
+					let mut v = AsRef::<[u8]>::as_ref(&s).to_vec();
+					v.resize(sl, 0);
+					S::from(v)
+				}
+				None => {
+					got.truncate(sl);
+					S::from(got)
+				}
+			})
+			.collect())
+	}
+
 	/// mod.rs:247-285: the first k shards, all present.
 	pub fn reconstruct_from_systematic<S: Shard>(&self, chunks: Vec<S>) -> Result<Vec<u8>> {
 		let ptrs: Vec<*const u8> = chunks.iter().map(|c| AsRef::<[u8]>::as_ref(c).as_ptr()).collect();

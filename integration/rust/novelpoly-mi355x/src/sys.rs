@@ -98,6 +98,26 @@ extern "C" {
 		out_capacity: usize,
 		out_len: *mut usize,
 	) -> c_int;
+	pub fn np_rs_restore_shards(
+		ctx: *mut np_ctx,
+		params: *const np_code_params,
+		shards: *const *const u8,
+		shard_lens: *const usize,
+		n_received: usize,
+		restored: *const *mut u8,
+		restored_len: usize,
+	) -> c_int;
+	pub fn np_restore_shards_batch_dev(
+		ctx: *mut np_ctx,
+		params: *const np_code_params,
+		d_shards: *mut u8,
+		shard_len: usize,
+		batch_stride: usize,
+		d_present: *const u8,
+		batch: usize,
+		d_status: *mut np_payload_status,
+		stream: *mut c_void,
+	) -> c_int;
 	pub fn np_rs_reconstruct_from_systematic(
 		ctx: *mut np_ctx,
 		params: *const np_code_params,

@@ -148,6 +148,14 @@ struct np_ctx {
   size_t big_cap = size_t(2) << 30;  // scratch_cap_for: set at creation
   hipEvent_t big_done = nullptr;
   bool big_used = false;
+  // np_restore_shards_batch_dev: the decoded payloads of a slice, then its
+  // plan or scratch shard rows and its status.  Not d_big, which the
+  // reconstruct and the big / huge encodes of the same call use; ordered
+  // across streams through restore_done the same way.
+  DevBuf d_restore;
+  size_t restore_cap = size_t(256) << 20;  // big_cap / 8: set at creation
+  hipEvent_t restore_done = nullptr;
+  bool restore_used = false;
   // Host-memory batch pipeline (np_*_batch_host): per slot a stream and
   // device buffers for one sub-batch; created on first use.
   static constexpr int kPipe = 6;  // at most; pipe_slots() are used
@@ -607,7 +615,8 @@ int np_debug_bounds_check(np_ctx* c, uint32_t out[8]) {
   hipError_t e = HIP(hipDeviceSynchronize());
   if (e != hipSuccess) return dev_err(e);
   hipError_t (*const take[])(uint32_t*) = {np::bounds_take_generic, np::bounds_take_fast, np::bounds_take_res,
-                                            np::bounds_take_small, np::bounds_take_big, np::bounds_take_huge};
+                                            np::bounds_take_small, np::bounds_take_big, np::bounds_take_huge,
+                                            np::bounds_take_restore};
   for (auto f : take) {
     uint32_t r[8];
     e = f(r);
@@ -683,6 +692,7 @@ int np_ctx_create(int device, np_ctx** out) {
   if (!c) return fail(NP_ERR_ALLOC);
   c->device = device;
   c->big_cap = scratch_cap_for(device);
+  c->restore_cap = c->big_cap / 8;
   hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
   const np::HostTables& t = np::host_tables();
   if (e == hipSuccess) e = upload(c, t.log, &c->T.log);
@@ -726,6 +736,8 @@ void np_ctx_destroy(np_ctx* c) {
   c->d_present.release();
   c->d_big.release();
   if (c->big_done) (void)hipEventDestroy(c->big_done);
+  c->d_restore.release();
+  if (c->restore_done) (void)hipEventDestroy(c->restore_done);
   for (int i = 0; i < np_ctx::kPipe; ++i) {
     if (c->pipe_s[i]) (void)hipStreamSynchronize(c->pipe_s[i]);
     c->pipe_in[i].release();
@@ -1367,7 +1379,103 @@ int reconstruct_dev2(np_ctx* c, const np_code_params* p, const uint8_t* d_shards
   return dev_err(HIP(launch_reconstruct(c, a, pick(c, stream))));
 }
 
+size_t align256(size_t x) { return (x + 255) / 256 * 256; }
+
+// Restore scratch of `want` bytes, ordered after every earlier restore of this
+// context on any stream (as big_scratch).  Caller holds the context lock.
+hipError_t restore_scratch(np_ctx* c, size_t want, hipStream_t s, uint8_t** out) {
+  hipError_t e = hipSuccess;
+  if (!c->restore_done) e = HIP(hipEventCreateWithFlags(&c->restore_done, hipEventDisableTiming));
+  if (e == hipSuccess && c->restore_used) {
+    if (want > c->d_restore.cap) e = HIP(hipEventSynchronize(c->restore_done));  // about to free the old buffer
+    if (e == hipSuccess) e = HIP(hipStreamWaitEvent(s, c->restore_done, 0));
+  }
+  if (e == hipSuccess) {
+    e = HIP(c->d_restore.ensure(want));
+    if (e != hipSuccess) e = hipErrorOutOfMemory;  // NP_ERR_ALLOC
+  }
+  *out = c->d_restore.as<uint8_t>();
+  return e;
+}
+
+// np_restore_shards_batch_dev after validation: per slice of the batch, the
+// reconstruct into the payload scratch, then either the row-masked encode
+// straight into d_shards or the unchanged encode into scratch rows and the
+// copy of the absent ones.  Caller holds the context lock.
+hipError_t launch_restore(np_ctx* c, const np_code_params* p, uint8_t* d_shards, size_t shard_len, size_t bstride,
+                          const uint8_t* d_present, size_t batch, uint32_t* d_status, hipStream_t s) {
+  const uint32_t n = static_cast<uint32_t>(p->n), k = static_cast<uint32_t>(p->k);
+  const uint32_t wanted_n = static_cast<uint32_t>(p->wanted_n);
+  const bool direct = np::masked_encode_supported(n, k);
+  const size_t pay_len = (shard_len / 2) * 2 * p->k;
+  const size_t rows_len = direct ? 0 : p->wanted_n * shard_len;  // scratch shard rows per payload
+  const size_t plan_len = direct ? np::restore_plan_words(n, k) * sizeof(uint32_t) : 0;
+  const size_t own_status = d_status ? 0 : kStatusBytes;
+  // The cap bounds the decoded payloads of a slice, and its scratch shard rows
+  // likewise (the plan and status come on top: bytes per payload).  Slices are
+  // multiples of 8 payloads where they can be: the fast kernels place a
+  // payload's tiles on one XCD only then (fast_common.hpp tile_of), and a slice
+  // of 1023 measured 1.5-1.7 x the reconstruct time of one of 1024.
+  size_t per = c->restore_cap / std::max(pay_len, rows_len);
+  per = per >= 8 ? per & ~size_t(7) : std::max<size_t>(1, per);
+  for (size_t b0 = 0; b0 < batch; b0 += per) {
+    const size_t cnt = std::min(per, batch - b0);
+    const size_t o_rows = align256(cnt * pay_len), o_plan = o_rows + align256(cnt * rows_len);
+    const size_t o_status = o_plan + align256(cnt * plan_len);
+    uint8_t* scr = nullptr;
+    hipError_t e = restore_scratch(c, o_status + align256(cnt * own_status), s, &scr);
+    if (e != hipSuccess) return e;
+    uint8_t* shards = d_shards + b0 * bstride;
+    np::ReconstructArgs a{};
+    a.shards = shards;
+    a.shard_len = shard_len;
+    a.batch_stride = bstride;
+    a.present = d_present + b0 * p->n;
+    a.locators = nullptr;  // computed on the device
+    a.batch = cnt;
+    a.n = n;
+    a.k = k;
+    a.out = scr;
+    a.out_stride = pay_len;
+    a.status = d_status ? d_status + 2 * b0 : reinterpret_cast<uint32_t*>(scr + o_status);
+    e = launch_reconstruct(c, a, s);
+    if (e == hipSuccess && wanted_n) {
+      if (direct) {
+        uint32_t* plan = reinterpret_cast<uint32_t*>(scr + o_plan);
+        e = HIP(np::launch_restore_plan(a.present, a.status, n, k, wanted_n, cnt, plan, s));
+        if (e == hipSuccess)
+          e = HIP(np::launch_encode_masked(c->T, enc_args(p, scr, pay_len, pay_len, cnt, shards, bstride), plan, s));
+      } else {
+        uint8_t* rows = scr + o_rows;
+        e = launch_encode(c, enc_args(p, scr, pay_len, pay_len, cnt, rows, rows_len), s);
+        if (e == hipSuccess)
+          e = HIP(np::launch_copy_absent_rows(rows, rows_len, shards, bstride, shard_len, a.present, a.status, n,
+                                              wanted_n, cnt, s));
+      }
+    }
+    if (e != hipSuccess) return e;
+    c->restore_used = true;
+    e = HIP(hipEventRecord(c->restore_done, s));
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 }  // namespace
+
+int np_restore_shards_batch_dev(np_ctx* c, const np_code_params* p, uint8_t* d_shards, size_t shard_len,
+                                size_t bstride, const uint8_t* d_present, size_t batch, np_payload_status* d_status,
+                                void* stream) {
+  if (!c) return fail(NP_ERR_INVALID_ARGUMENT);
+  int st = check_params(p);
+  if (st) return st;
+  if (shard_len == 0 || (shard_len & 1)) return fail(NP_ERR_EMPTY_SHARD);
+  if (!d_shards || !d_present || bstride < p->n * shard_len) return fail(NP_ERR_INVALID_ARGUMENT);
+  std::lock_guard<std::mutex> g(c->mu);  // context scratch
+  (void)hipSetDevice(c->device);
+  return dev_err(launch_restore(c, p, d_shards, shard_len, bstride, d_present, batch,
+                                reinterpret_cast<uint32_t*>(d_status), pick(c, stream)));
+}
 
 int np_reconstruct_batch_dev3(np_ctx* c, const np_code_params* p, const uint8_t* d_shards, size_t shard_len,
                               size_t bstride, const uint8_t* d_present, const uint16_t* d_loc, size_t batch,
@@ -1502,6 +1610,61 @@ int np_rs_reconstruct(np_ctx* c, const np_code_params* p, const uint8_t* const* 
   if (e != hipSuccess) return dev_err(e);
   std::memcpy(out, c->h_out.p, need);
   *out_len = need;
+  return NP_OK;
+}
+
+int np_rs_restore_shards(np_ctx* c, const np_code_params* p, const uint8_t* const* shards, const size_t* lens,
+                         size_t n_received, uint8_t* const* restored, size_t restored_len) {
+  // validation as np_rs_reconstruct (mod.rs:163-214)
+  if (!c || !p || (n_received && (!shards || !lens))) return fail(NP_ERR_INVALID_ARGUMENT);
+  if (!is_pow2(p->n) && !is_pow2(p->k)) return fail(NP_ERR_PARAMETER_MUST_BE_POWER_OF_2, p->n, p->k);
+  const size_t n = p->n, k = p->k;
+  std::vector<uint8_t> present(n, 0);
+  size_t have = 0;
+  for (size_t i = 0; i < n && i < n_received; ++i) {
+    present[i] = shards[i] ? 1 : 0;
+    have += present[i];
+  }
+  if (have < k) return fail(NP_ERR_NEED_MORE_SHARDS, have, k, n);
+  size_t first = 0;
+  while (!present[first]) ++first;
+  const size_t syms = (lens[first] + 1) / 2;
+  if (syms == 0) return fail(NP_ERR_EMPTY_SHARD);
+  for (size_t i = first + 1; i < n; ++i)
+    if (present[i] && (lens[i] + 1) / 2 != syms) return fail(NP_ERR_INCONSISTENT_SHARD_LENGTHS, syms, (lens[i] + 1) / 2);
+  int st = check_params(p);
+  if (st) return st;
+  const size_t sl = 2 * syms;
+  if (!restored || restored_len < sl) return fail(NP_ERR_INVALID_ARGUMENT, sl);
+  std::lock_guard<std::mutex> g(c->mu);
+  (void)hipSetDevice(c->device);
+  hipError_t e = HIP(c->h_in.ensure(n * sl));
+  if (e == hipSuccess) e = HIP(c->d_in.ensure(n * sl));
+  if (e == hipSuccess) e = HIP(c->d_present.ensure(n));
+  if (e == hipSuccess) e = HIP(c->h_pres.ensure(n));
+  if (e != hipSuccess) return dev_err(e);
+  std::memcpy(c->h_pres.p, present.data(), n);
+  uint8_t* stage = c->h_in.as<uint8_t>();
+  for (size_t i = 0; i < n; ++i) {
+    uint8_t* row = stage + i * sl;
+    if (present[i]) {
+      std::memcpy(row, shards[i], lens[i]);
+      if (lens[i] < sl) std::memset(row + lens[i], 0, sl - lens[i]);  // WrappedShard zero pad
+    } else {
+      std::memset(row, 0, sl);
+    }
+  }
+  hipStream_t s = c->stream;
+  e = HIP(hipMemcpyAsync(c->d_in.p, stage, n * sl, hipMemcpyHostToDevice, s));
+  if (e == hipSuccess) e = HIP(hipMemcpyAsync(c->d_present.p, c->h_pres.p, n, hipMemcpyHostToDevice, s));
+  if (e == hipSuccess)
+    e = launch_restore(c, p, c->d_in.as<uint8_t>(), sl, n * sl, c->d_present.as<uint8_t>(), 1, nullptr, s);
+  // the rows come back through the same pinned staging (the received ones unchanged)
+  if (e == hipSuccess) e = HIP(hipMemcpyAsync(stage, c->d_in.p, p->wanted_n * sl, hipMemcpyDeviceToHost, s));
+  if (e == hipSuccess) e = HIP(hipStreamSynchronize(s));
+  if (e != hipSuccess) return dev_err(e);
+  for (size_t i = 0; i < p->wanted_n; ++i)
+    if (!present[i] && restored[i]) std::memcpy(restored[i], stage + i * sl, sl);
   return NP_OK;
 }
 

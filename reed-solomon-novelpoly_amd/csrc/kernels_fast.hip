@@ -237,6 +237,262 @@ __global__ __launch_bounds__(4 * K) __attribute__((amdgpu_waves_per_eu(4))) void
   for (uint32_t sh = 4; sh < nshift && sh * K < a.wanted_n; ++sh) shift(Int<0>{}, sh);
 }
 
+// --------------------------------------------------------- masked encode ----
+// np_restore_shards_batch_dev: k_encode_fast's flow on a reconstructed payload,
+// storing only the rows of the payload's plan (launchers.hpp restore_plan_words:
+// absent rows below wanted_n of a decoded payload, from k_restore_plan) into
+// the buffer that holds the received rows.  The plan is read with scalar
+// loads: one word of segment bits decides what the workgroup runs, 16 row bits
+// per wave and pass what it stores.
+//  - no row to restore: the workgroup exits before the tile load;
+//  - none in [K, wanted_n): it stores its absent systematic rows and exits
+//    before the inverse transform;
+//  - shift s runs only when segment s holds a row to restore; the tables of
+//    the other shifts are not staged;
+//  - inside a shift's cq levels a wave runs only the butterfly groups that
+//    feed one of its rows to restore (cq_levels `rows`).
+// Every exit is workgroup-uniform and sits before the barrier it would miss.
+
+// First segment >= from with its plan bit set, or nseg (wave-uniform).
+__device__ __forceinline__ uint32_t next_segment(cpool_t seg, uint32_t from, uint32_t nseg) {
+  uint32_t r = nseg;
+  for (uint32_t w = from >> 5; 32u * w < nseg; ++w) {
+    uint32_t x = seg[w];
+    if (w == (from >> 5)) x &= ~0u << (from & 31u);
+    if (x) {
+      r = 32u * w + static_cast<uint32_t>(__builtin_ctz(x));
+      break;
+    }
+  }
+  return uniform(r);
+}
+
+// The table choices of stage_vpools are scalar selects: their conditions must
+// be in SGPRs whatever the compiler proves about a shift number.
+__device__ __forceinline__ bool uniform_b(bool v) { return uniform(v ? 1u : 0u) != 0; }
+// enc_conv(K, sh) of a runtime shift (gen_of(sh K) >= 1 is sh K >= 256), inlined.
+template <int K>
+__device__ __forceinline__ bool enc_conv_u(uint32_t sh) {
+  static_assert(!enc_conv(K, 0) && enc_conv(K, 1) == (K >= 256) && enc_conv(K, 2) == (2 * K >= 256) &&
+                    enc_conv(K, 3) == (3 * K >= 256) && !enc_conv(K, 4),
+                "enc_conv");
+  return uniform_b(sh >= 1u && sh <= 3u && sh * K >= 256u);
+}
+
+// Bit p: row row0 + p is restored (row0 a multiple of 16, wave-uniform).
+__device__ __forceinline__ uint32_t restore_mask16(cpool_t rows, uint32_t row0) {
+  return uniform((rows[row0 >> 5] >> (row0 & 16u)) & 0xffffu);
+}
+
+// store_rows for the rows of `mask` only (wave-uniform: a scalar branch per row).
+__device__ __forceinline__ void store_rows_masked(uint8_t* out, size_t shard_len, uint32_t row0, uint32_t mask,
+                                                  const uint32_t (&L)[16], const uint32_t (&H)[16], uint32_t lane,
+                                                  uint32_t ncols, bool full, bool nt) {
+  if (mask == 0) return;
+  if (full && 16 * shard_len < 0x7fffffffu) {
+    // (the descriptor spans 16 rows; only rows of the mask, all below wanted_n, are accessed)
+    const __amdgpu_buffer_rsrc_t r = buf_rsrc(out + static_cast<size_t>(row0) * shard_len, 16 * static_cast<uint32_t>(shard_len));
+    if (nt) {
+#pragma unroll
+      for (int p = 0; p < 16; ++p)
+        if ((mask >> p) & 1u) {
+          const uint2 v = cq_row(L[p], H[p]);
+          __builtin_amdgcn_raw_buffer_store_b64(u32x2{v.x, v.y}, r, 8u * lane,
+                                                static_cast<uint32_t>(p * shard_len), kRowStoreCpol);
+        }
+    } else {
+#pragma unroll
+      for (int p = 0; p < 16; ++p)
+        if ((mask >> p) & 1u) {
+          const uint2 v = cq_row(L[p], H[p]);
+          __builtin_amdgcn_raw_buffer_store_b64(u32x2{v.x, v.y}, r, 8u * lane, static_cast<uint32_t>(p * shard_len), 0);
+        }
+    }
+  } else if (4 * lane + 4 <= ncols) {  // partial tile, lanes with all four columns
+#pragma unroll
+    for (int p = 0; p < 16; ++p)
+      if ((mask >> p) & 1u) *reinterpret_cast<uint2*>(out + static_cast<size_t>(row0 + p) * shard_len + 8u * lane) = cq_row(L[p], H[p]);
+  } else {
+#pragma unroll
+    for (int p = 0; p < 16; ++p)
+      if ((mask >> p) & 1u) store4(out + static_cast<size_t>(row0 + p) * shard_len, cq_row(L[p], H[p]), lane, ncols, false);
+  }
+}
+
+// shift_cq for the output rows of `rows` only.
+template <int K, int SH>
+__device__ __forceinline__ void shift_cq_rows(const DevTables& T, const uint32_t* vp, uint32_t index, uint32_t g,
+                                              uint32_t (&XL)[16], uint32_t (&XH)[16], uint32_t rows) {
+  if constexpr (SH == 0) {
+    cq_levels<K, false, false, -1, false, kEncPrioCq>(T, vp, index, g, XL, XH, rows);
+  } else {
+    cq_levels<K, false, false, kShiftGen<K, SH>, kEncConv<K, SH>, kEncPrioCq>(T, vp, index, g, XL, XH, rows);
+    if constexpr (!kEncConv<K, SH>) tower_convert(T, XL, XH);  // back to Cantor coordinates for the shard rows
+  }
+}
+
+// SH of shift 3 when shift 1 or 2 was skipped: fwd_top's MODE 3 takes shift
+// 3's top-level products from PL / PH, where shifts 1 and 2 leave them; this
+// instance multiplies for itself (MODE 0).
+constexpr int kShift3Own = 30;
+
+template <int K>
+__global__ __launch_bounds__(4 * K) __attribute__((amdgpu_waves_per_eu(4))) void k_encode_masked(
+    DevTables T, EncodeArgs a, uint32_t nchunks, uint32_t tiles, const uint32_t* plan) {
+  using G = Geo<K>;
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  uint8_t* tile = smem;
+  uint32_t* VP = reinterpret_cast<uint32_t*>(smem + G::kTileBytes);  // up to 4 staged transforms
+  const uint32_t nshift = a.n / K;
+  const uint32_t segw = static_cast<uint32_t>(restore_seg_words(a.n, K));
+  const uint32_t planw = static_cast<uint32_t>(restore_plan_words(a.n, K));
+#if NP_BOUNDS_CHECK
+  {
+    BoundsSet b = bounds_of_enc(a);
+    b.lo[kBkRecords] = reinterpret_cast<uint64_t>(plan);
+    b.hi[kBkRecords] = b.lo[kBkRecords] + a.batch * planw * 4u;
+    bounds_arm(b);
+  }
+#endif
+  const TileRef tr = tile_of(blockIdx.x, tiles, (a.batch & 7u) == 0);
+  const uint32_t pb = tr.pb, tl = tr.tl;
+  NP_BNOTE(plan + static_cast<size_t>(pb) * planw, 4u * planw, kBkRecords);
+  const cpool_t seg = (cpool_t)(plan) + static_cast<size_t>(pb) * planw;
+  const cpool_t rowbits = seg + segw;
+  const bool seg0 = (seg[0] & 1u) != 0;
+  const uint32_t first = next_segment(seg, 1, nshift);  // the first shift to run
+  if (!seg0 && first == nshift) return;                 // nothing to restore (or NeedMoreShards)
+  const uint32_t ch0 = tl * kTile;
+  const uint32_t ncols = min(static_cast<uint32_t>(kTile), nchunks - ch0);
+  const uint8_t* pay = a.payloads + static_cast<size_t>(pb) * a.payload_stride;
+  uint8_t* out = a.shards + static_cast<size_t>(pb) * a.batch_stride + 2 * static_cast<size_t>(ch0);
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, g = uniform(tid >> 6);
+  const bool full = ncols == kTile && rows_vec_ok(a.shards, a.batch_stride, a.shard_len);
+
+  // ---- tile load (as k_encode_fast)
+  {
+    const uint32_t c0 = tid / G::Q, m0 = tid % G::Q;
+    const uint32_t base = col_base<K>(c0) ^ (8u * m0);
+    const size_t gbase = static_cast<size_t>(ch0 + c0) * 2 * K + 8u * m0;
+    const bool fast = out_vec_ok(pay, 0) && static_cast<size_t>(ch0 + kTile) * 2 * K <= a.payload_len;
+    if (fast) {
+      uint2 v[16];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) v[i] = load_once(pay + gbase + static_cast<size_t>(i) * 32 * K);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) *reinterpret_cast<uint2*>(tile + (base ^ col_base_c<K>(16u * i))) = v[i];
+    } else {
+#pragma unroll 1
+      for (uint32_t i = 0; i < 16; ++i) {
+        const size_t g0 = gbase + static_cast<size_t>(i) * 32 * K;
+        uint32_t w[2] = {0, 0};
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (g0 + e < a.payload_len) w[e >> 2] |= static_cast<uint32_t>(*NP_BCHK(pay + (g0 + e), 1, kBkPayloads)) << (8 * (e & 3));
+        *reinterpret_cast<uint2*>(tile + (base ^ col_base_c<K>(16u * i))) = make_uint2(w[0], w[1]);
+      }
+    }
+  }
+  const bool nt = rows_nt(a.shards, a.batch_stride, a.shard_len);
+  // n <= 4K: one table buffer per transform that runs; otherwise two buffers
+  // alternate, each shift staging the next one that runs
+  const bool resident = nshift <= 4;
+  if (first < nshift) {
+    stage_vpools<K, G::kThreads>(T, 0, VP, true);  // inverse transform, index 0
+    if (resident) {
+      for (uint32_t sh = first; sh < nshift; sh = next_segment(seg, sh + 1, nshift))
+        stage_vpools<K, G::kThreads>(T, sh * K, VP + sh * G::kVPWords, true, enc_conv_u<K>(sh));
+    } else {
+      stage_vpools<K, G::kThreads>(T, first * K, VP + G::kVPWords, uniform_b(first < 4), enc_conv_u<K>(first));
+    }
+  }
+  __syncthreads();
+
+  const uint32_t cqb = col_base<K>(4 * lane) ^ (32u * g);  // blocks 4g..4g+3 of columns 4l..4l+3
+  // ---- cq pass: absent systematic rows, inverse levels 0..3
+  {
+    uint32_t CL[16], CH[16];
+    cq_read<K>(tile, cqb, CL, CH);
+    if (seg0) store_rows_masked(out, a.shard_len, 16 * g, restore_mask16(rowbits, 16 * g), CL, CH, lane, ncols, full, nt);
+    if (first == nshift) return;  // no parity row to restore
+    tower_convert(T, CL, CH);     // transforms run in tower coordinates
+    cq_levels<K, true, true, 0, false, kEncPrioCq>(T, VP, 0, g, CL, CH);
+    // the quad items overlay payload blocks that other waves read: wait for
+    // every wave's cq_read
+    __syncthreads();
+    cq_write_q(tile, g, lane, CL, CH);
+  }
+  __syncthreads();
+  // ---- high layout: inverse levels 4.. -> coefficients M
+  uint32_t ML[16], MH[16];
+  hi_read_q<K>(tile, g, lane, ML, MH);
+  hi_levels<K, true, true, 0, 0, kEncPrio>(T, VP, 0, ML, MH);
+#pragma unroll
+  for (int q = 0; q < 16; ++q) asm volatile("" : "+v"(ML[q]), "+v"(MH[q]));  // materialise M once
+
+  // top-level products of shift 1, then of shifts 1 ^ 2 (fwd_top); zero, so that
+  // a shift 2 without shift 1 accumulates into defined values (which nobody reads)
+  uint32_t PL[8] = {}, PH[8] = {};
+  uint32_t slot = 1;  // !resident: the table buffer of the shift that runs
+  // shift sh; nxt: the next shift that runs (nshift: none)
+  auto shift = [&](auto shc, uint32_t sh, uint32_t nxt) __attribute__((always_inline)) {
+    constexpr int SH = decltype(shc)::value;
+    constexpr int SHC = SH == kShift3Own ? 3 : SH;
+    const uint32_t index = sh * K;
+    uint32_t XL[16], XH[16];
+    const uint32_t* vp = VP + (resident ? sh : slot) * G::kVPWords;
+    if constexpr (SH == kShift3Own) {
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        XL[q] = ML[q];
+        XH[q] = MH[q];
+      }
+      fwd_top<K, 0, 0>(T, vp, index, XL, XH, PL, PH);
+      hi_levels<K, false, false, 1, 0, kEncPrio>(T, vp, index, XL, XH);
+    } else {
+      shift_hi<K, SH>(T, vp, index, ML, MH, XL, XH, PL, PH);
+    }
+    __syncthreads();  // the previous cq pass is done with the tile and with the other table buffer
+    if (!resident && nxt < nshift)
+      stage_vpools<K, G::kThreads>(T, nxt * K, VP + (slot ^ 1u) * G::kVPWords, uniform_b(nxt < 4),
+                                   enc_conv_u<K>(nxt));
+    hi_write_q<K>(tile, g, lane, XL, XH);
+    __syncthreads();
+    cq_read_q(tile, g, lane, XL, XH);
+    const uint32_t mask = restore_mask16(rowbits, index + 16 * g);
+    shift_cq_rows<K, SHC>(T, vp, index, g, XL, XH, mask);
+    store_rows_masked(out, a.shard_len, index + 16 * g, mask, XL, XH, lane, ncols, full, nt);
+    slot ^= 1u;
+  };
+  const bool own3 = ((seg[0] >> 1) & 3u) != 3u;  // shift 1 or 2 skipped
+  // cur: the next shift to run; nshift (2 at n = 2K: not "shift 2") when none is left
+  uint32_t cur = first;
+  if (cur == 1) {
+    const uint32_t nxt = next_segment(seg, 2, nshift);
+    shift(Int<1>{}, 1, nxt);
+    cur = nxt;
+  }
+  if (cur == 2 && cur < nshift) {
+    const uint32_t nxt = next_segment(seg, 3, nshift);
+    shift(Int<2>{}, 2, nxt);
+    cur = nxt;
+  }
+  if (cur == 3 && cur < nshift) {
+    const uint32_t nxt = next_segment(seg, 4, nshift);
+    if (own3)
+      shift(Int<kShift3Own>{}, 3, nxt);
+    else
+      shift(Int<3>{}, 3, nxt);
+    cur = nxt;
+  }
+#pragma unroll 1
+  while (cur < nshift) {
+    const uint32_t nxt = next_segment(seg, cur + 1, nshift);
+    shift(Int<0>{}, cur, nxt);
+    cur = nxt;
+  }
+}
+
 // ----------------------------------------------------- multi-tile encode ----
 // k = 256: a workgroup encodes `tpw` consecutive tiles of one payload, and the
 // payload blocks of the next tile flow into the LDS tile by LDS-DMA while the
@@ -1533,6 +1789,10 @@ hipError_t launch_reconstruct_fast(const DevTables& T, const ReconstructArgs& a,
   }
 }
 
+namespace {
+hipError_t configure_masked_kernels();  // below, with the masked encode's launchers
+}
+
 hipError_t configure_fast_kernels() {
   hipError_t e = hipSuccess;
   auto set = [&](const void* f, size_t bytes) {
@@ -1558,9 +1818,58 @@ hipError_t configure_fast_kernels() {
   set(reinterpret_cast<const void*>(&k_reconstruct_fast<128, 8, 8>), reconstruct_lds_bytes<128, 8>());
   set(reinterpret_cast<const void*>(&k_reconstruct_fast<256, 8, 2>), reconstruct_lds_bytes<256, 8>());
   set(reinterpret_cast<const void*>(&k_reconstruct_fast<256, 8, 8>), reconstruct_lds_bytes<256, 8>());
+  if (e == hipSuccess) e = configure_masked_kernels();
   return e;
 }
 
 hipError_t bounds_take_fast(uint32_t out[8]) { return bounds_take_tu(out); }
+
+// ------------------------------------------- masked encode: launchers ----
+// The last references in this file, so that k_encode_masked's instances come
+// after every older kernel in the code object (the older kernels' assembly,
+// block labels included, stays what it was: tools/isa_funcdiff.py).
+namespace {
+
+// One tile per workgroup at every K: the multi-tile encode counts its
+// outstanding row stores, which a masked pass does not issue.
+template <int K>
+hipError_t launch_encode_masked_k(const DevTables& T, const EncodeArgs& a, const uint32_t* plan, hipStream_t s) {
+  const size_t nchunks = (a.payload_len + 2 * a.k - 1) / (2 * a.k);
+  if (nchunks == 0 || a.batch == 0) return hipSuccess;
+  if (nchunks > 0xffffffffu) return hipErrorInvalidValue;
+  const uint32_t tiles = static_cast<uint32_t>((nchunks + kTile - 1) / kTile);
+  const size_t blocks = a.batch * tiles;
+  if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
+  k_encode_masked<K><<<static_cast<uint32_t>(blocks), Geo<K>::kThreads, encode_lds_bytes<K>(), s>>>(
+      T, a, static_cast<uint32_t>(nchunks), tiles, plan);
+  return hipGetLastError();
+}
+
+hipError_t configure_masked_kernels() {
+  hipError_t e = hipSuccess;
+  auto set = [&](const void* f, size_t bytes) {
+    hipError_t r = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
+    if (r != hipSuccess && e == hipSuccess) e = r;
+  };
+  set(reinterpret_cast<const void*>(&k_encode_masked<64>), encode_lds_bytes<64>());
+  set(reinterpret_cast<const void*>(&k_encode_masked<128>), encode_lds_bytes<128>());
+  set(reinterpret_cast<const void*>(&k_encode_masked<256>), encode_lds_bytes<256>());
+  return e;
+}
+
+}  // namespace
+
+bool masked_encode_supported(uint32_t n, uint32_t k) {
+  return (k == 64 || k == 128 || k == 256) && n >= 2 * k && n <= 65536;
+}
+
+hipError_t launch_encode_masked(const DevTables& T, const EncodeArgs& a, const uint32_t* plan, hipStream_t s) {
+  switch (a.k) {
+    case 64: return launch_encode_masked_k<64>(T, a, plan, s);
+    case 128: return launch_encode_masked_k<128>(T, a, plan, s);
+    case 256: return launch_encode_masked_k<256>(T, a, plan, s);
+    default: return hipErrorNotSupported;
+  }
+}
 
 }  // namespace np

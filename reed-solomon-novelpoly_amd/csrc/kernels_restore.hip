@@ -1,0 +1,144 @@
+// Restoring absent shard rows (np_restore_shards_batch_dev, engine.cpp): the
+// small kernels around the encode that follows the reconstruct.
+//
+//  * k_restore_plan -- per payload, which rows the row-masked fast encode
+//    (kernels_fast.hip k_encode_masked) stores and which size-k segments hold
+//    one, as bit words that kernel reads with scalar loads: one pass over the
+//    n present flags per payload instead of one per column tile.
+//  * k_copy_absent_rows -- every shape without a masked encode: the unchanged
+//    encode writes all rows below wanted_n to a scratch shard buffer, and this
+//    kernel copies the absent rows of the decoded payloads to the caller's
+//    buffer (HBM to HBM, any even row address).
+#include <algorithm>
+
+#include "device_common.hpp"
+#include "launchers.hpp"
+
+namespace np {
+namespace {
+
+constexpr uint32_t kPlanThreads = 256;
+
+// One workgroup per payload.  A wave takes 64 consecutive rows at a time (one
+// flag byte per lane, a ballot): two row words, and one bit of the segment
+// words (64 rows never straddle a segment: k >= 64).
+__global__ __launch_bounds__(kPlanThreads) void k_restore_plan(const uint8_t* __restrict__ present,
+                                                               const uint32_t* __restrict__ status, uint32_t n,
+                                                               uint32_t k, uint32_t wanted_n, size_t batch,
+                                                               uint32_t* __restrict__ plan) {
+  __shared__ uint32_t seg[32];  // n / k <= 1024 segments
+  const uint32_t pb = blockIdx.x, tid = threadIdx.x, lane = tid & 63u;
+  const uint32_t segw = static_cast<uint32_t>(restore_seg_words(n, k));
+  const size_t words = restore_plan_words(n, k);
+#if NP_BOUNDS_CHECK
+  {
+    BoundsSet b{};
+    b.lo[kBkPresent] = reinterpret_cast<uint64_t>(present);
+    b.hi[kBkPresent] = b.lo[kBkPresent] + batch * n;
+    b.lo[kBkStatus] = reinterpret_cast<uint64_t>(status);
+    b.hi[kBkStatus] = b.lo[kBkStatus] + batch * 8;
+    b.lo[kBkRecords] = reinterpret_cast<uint64_t>(plan);
+    b.hi[kBkRecords] = b.lo[kBkRecords] + batch * words * 4;
+    bounds_arm(b);
+  }
+#endif
+  if (tid < 32) seg[tid] = 0;
+  __syncthreads();
+  const bool ok = *NP_BCHK(status + 2 * static_cast<size_t>(pb), 4, kBkStatus) == 0;
+  const uint8_t* pres = present + static_cast<size_t>(pb) * n;
+  uint32_t* pl = plan + static_cast<size_t>(pb) * words;
+  for (uint32_t v0 = tid - lane; v0 < n; v0 += kPlanThreads) {  // n is a multiple of 64
+    const uint32_t v = v0 + lane;
+    const bool absent = ok && v < wanted_n && *NP_BCHK(pres + v, 1, kBkPresent) == 0;
+    const uint64_t m = __ballot(absent);
+    if (lane == 0) {
+      *NP_BCHK(pl + segw + v0 / 32, 8, kBkRecords) = static_cast<uint32_t>(m);
+      pl[segw + v0 / 32 + 1] = static_cast<uint32_t>(m >> 32);
+      if (m) atomicOr(&seg[(v0 / k) >> 5], 1u << ((v0 / k) & 31u));
+    }
+  }
+  __syncthreads();
+  if (tid < segw) *NP_BCHK(pl + tid, 4, kBkRecords) = seg[tid];
+}
+
+constexpr uint32_t kCopyWaves = 4;
+constexpr size_t kCopyChunk = 4096;
+
+// One wave per 4 KiB piece of a row (as k_copy_rows, kernels_systematic.hip).
+__global__ __launch_bounds__(64 * kCopyWaves) void k_copy_absent_rows(const uint8_t* __restrict__ src, size_t sstride,
+                                                                     uint8_t* __restrict__ dst, size_t dstride,
+                                                                     size_t row_bytes,
+                                                                     const uint8_t* __restrict__ present,
+                                                                     const uint32_t* __restrict__ status, uint32_t n,
+                                                                     uint32_t rows, size_t count, size_t chunks,
+                                                                     size_t total) {
+  const uint32_t lane = threadIdx.x & 63;
+#if NP_BOUNDS_CHECK
+  {
+    BoundsSet b{};
+    b.lo[kBkPresent] = reinterpret_cast<uint64_t>(present);
+    b.hi[kBkPresent] = b.lo[kBkPresent] + count * n;
+    b.lo[kBkStatus] = reinterpret_cast<uint64_t>(status);
+    b.hi[kBkStatus] = b.lo[kBkStatus] + count * 8;
+    b.lo[kBkPayloads] = reinterpret_cast<uint64_t>(src);  // the encode's scratch rows
+    b.hi[kBkPayloads] = b.lo[kBkPayloads] + (count - 1) * sstride + rows * row_bytes;
+    b.lo[kBkShards] = reinterpret_cast<uint64_t>(dst);
+    b.hi[kBkShards] = b.lo[kBkShards] + (count - 1) * dstride + rows * row_bytes;
+    bounds_arm(b);
+  }
+#endif
+  const size_t waves = static_cast<size_t>(gridDim.x) * kCopyWaves;
+  const uintptr_t al = reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | sstride | dstride | row_bytes;
+  const bool vec = (al & 15) == 0, vec4 = (al & 3) == 0;
+  for (size_t u = static_cast<size_t>(blockIdx.x) * kCopyWaves + (threadIdx.x >> 6); u < total; u += waves) {
+    const size_t r = u / chunks, ch = u - r * chunks;
+    const size_t b = r / rows, v = r - b * rows;
+    if (*NP_BCHK(present + (b * n + v), 1, kBkPresent) != 0 || *NP_BCHK(status + 2 * b, 4, kBkStatus) != 0) continue;
+    const size_t off = ch * kCopyChunk, len = row_bytes - off < kCopyChunk ? row_bytes - off : kCopyChunk;
+    const uint8_t* s = src + b * sstride + v * row_bytes + off;
+    uint8_t* d = dst + b * dstride + v * row_bytes + off;
+    NP_BNOTE(s, len, kBkPayloads);
+    NP_BNOTE(d, len, kBkShards);
+    if (vec) {
+      const uint4* s4 = reinterpret_cast<const uint4*>(s);
+      uint4* d4 = reinterpret_cast<uint4*>(d);
+      for (size_t i = lane; i < len / 16; i += 64) d4[i] = s4[i];
+    } else if (vec4) {
+      const uint32_t* s1 = reinterpret_cast<const uint32_t*>(s);
+      uint32_t* d1 = reinterpret_cast<uint32_t*>(d);
+      for (size_t i = lane; i < len / 4; i += 64) d1[i] = s1[i];
+    } else {  // rows are whole symbols at even addresses: 2-byte pieces
+      const uint16_t* s1 = reinterpret_cast<const uint16_t*>(s);
+      uint16_t* d1 = reinterpret_cast<uint16_t*>(d);
+      for (size_t i = lane; i < len / 2; i += 64) d1[i] = s1[i];
+    }
+  }
+}
+
+}  // namespace
+
+hipError_t launch_restore_plan(const uint8_t* present, const uint32_t* status, uint32_t n, uint32_t k,
+                               uint32_t wanted_n, size_t batch, uint32_t* plan, hipStream_t s) {
+  if (batch == 0) return hipSuccess;
+  if (batch > 0x7fffffffu || k < 64 || n % 64 != 0 || n / k > 1024) return hipErrorInvalidValue;
+  k_restore_plan<<<static_cast<uint32_t>(batch), kPlanThreads, 0, s>>>(present, status, n, k, wanted_n, batch, plan);
+  return hipGetLastError();
+}
+
+hipError_t launch_copy_absent_rows(const uint8_t* src, size_t sstride, uint8_t* dst, size_t dstride,
+                                   size_t row_bytes, const uint8_t* present, const uint32_t* status, uint32_t n,
+                                   uint32_t rows, size_t count, hipStream_t s) {
+  const size_t chunks = (row_bytes + kCopyChunk - 1) / kCopyChunk, total = count * rows * chunks;
+  if (total == 0) return hipSuccess;
+  const uintptr_t al = reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | sstride | dstride | row_bytes;
+  if (al & 1) return hipErrorInvalidValue;
+  const size_t grid = std::min<size_t>((total + kCopyWaves - 1) / kCopyWaves, 8192);
+  k_copy_absent_rows<<<static_cast<uint32_t>(grid), 64 * kCopyWaves, 0, s>>>(src, sstride, dst, dstride, row_bytes,
+                                                                            present, status, n, rows, count, chunks,
+                                                                            total);
+  return hipGetLastError();
+}
+
+hipError_t bounds_take_restore(uint32_t out[8]) { return bounds_take_tu(out); }
+
+}  // namespace np

@@ -177,4 +177,25 @@ constexpr size_t huge_side_bytes(size_t batch) { return (batch + 15) / 16 * 16 +
 hipError_t launch_reconstruct_huge(const DevTables& T, const ReconstructArgs& a, uint8_t* scratch, uint8_t* mode,
                                    uint16_t* locators, hipStream_t s);
 hipError_t configure_huge_kernels();
+
+// ---- restoring absent shard rows (np_restore_shards_batch_dev) ----
+// Per-payload plan of the row-masked encode (kernels_restore.hip writes it,
+// kernels_fast.hip k_encode_masked reads it with scalar loads): first
+// restore_seg_words(n, k) words with bit q set when rows [qk, (q+1)k) hold a row
+// to restore, then n / 32 words with bit v set when row v is one -- absent,
+// below wanted_n, and the payload's status (ReconstructArgs::status layout) OK.
+constexpr size_t restore_seg_words(uint32_t n, uint32_t k) { return (n / k + 31) / 32; }
+constexpr size_t restore_plan_words(uint32_t n, uint32_t k) { return restore_seg_words(n, k) + n / 32; }
+hipError_t launch_restore_plan(const uint8_t* present, const uint32_t* status, uint32_t n, uint32_t k,
+                               uint32_t wanted_n, size_t batch, uint32_t* plan, hipStream_t s);
+// k in {64, 128, 256}, every n of the fast encode: the single-tile encode that
+// stores only the plan's rows and skips the transforms of segments without one.
+bool masked_encode_supported(uint32_t n, uint32_t k);
+hipError_t launch_encode_masked(const DevTables& T, const EncodeArgs& a, const uint32_t* plan, hipStream_t s);
+// Every other shape: dst[b][v] = src[b][v] (row_bytes each, any even address)
+// for b < count, v < rows with present[b * n + v] == 0 and status[2 b] == 0.
+hipError_t launch_copy_absent_rows(const uint8_t* src, size_t sstride, uint8_t* dst, size_t dstride,
+                                   size_t row_bytes, const uint8_t* present, const uint32_t* status, uint32_t n,
+                                   uint32_t rows, size_t count, hipStream_t s);
+hipError_t bounds_take_restore(uint32_t out[8]);
 }  // namespace np

@@ -72,6 +72,8 @@ def lib() -> C.CDLL:
             "np_reconstruct_batch_dev3": (C.c_int, [vp, P, vp, _sz, _sz, vp, vp, _sz, vp, _sz, vp, vp]),
             "np_reconstruct_batch_dev2": (C.c_int, [vp, P, vp, _sz, _sz, vp, vp, _sz, vp, _sz, vp]),
             "np_reconstruct_codewords_batch_dev": (C.c_int, [vp, P, vp, _sz, _sz, vp, _sz, vp, _sz, vp, vp]),
+            "np_restore_shards_batch_dev": (C.c_int, [vp, P, vp, _sz, _sz, vp, _sz, vp, vp]),
+            "np_rs_restore_shards": (C.c_int, [vp, P, C.POINTER(vp), C.POINTER(_sz), _sz, C.POINTER(vp), _sz]),
             "np_error_locator_dev": (C.c_int, [vp, _sz, vp, _sz, vp, vp]),
             "np_reconstruct_from_systematic_batch_dev": (C.c_int, [vp, P, vp, _sz, _sz, _sz, vp, _sz, vp]),
             "np_encode_batch_host": (C.c_int, [vp, P, vp, _sz, _sz, _sz, vp, _sz]),
@@ -383,6 +385,21 @@ class ReedSolomon:
                                        C.byref(olen)))
         return out.raw[: olen.value]
 
+    def restore_shards(self, received: Sequence[Optional[bytes]]) -> List[bytes]:
+        """All ``wanted_n`` shards of ``encode(reconstruct(received))``: the
+        received ones as given (padded to an even length), the absent ones
+        restored (np_rs_restore_shards)."""
+        ptrs, lens, keep = _shard_arrays(received)
+        sl = 2 * max([(len(_as_bytes(s)) + 1) // 2 for s in received[: self.n] if s is not None] or [0])
+        absent =[i for i in range(self.wanted_n) if i >= len(received) or received[i] is None]
+        bufs = {i: C.create_string_buffer(max(1, sl)) for i in absent}
+        outs = (C.c_void_p * max(1, self.wanted_n))()
+        for i, b in bufs.items():
+            outs[i] = C.cast(b, C.c_void_p)
+        _raise(lib().np_rs_restore_shards(self.ctx.handle, C.byref(self._p), ptrs, lens, len(received), outs, sl))
+        return [bufs[i].raw[:sl] if i in bufs else WrappedShard(_as_bytes(received[i])).inner
+                for i in range(self.wanted_n)]
+
     def reconstruct_from_systematic(self, chunks: Sequence[bytes]) -> bytes:
         ptrs, lens, keep = _shard_arrays(chunks)
         maxsyms = max([(len(_as_bytes(s)) + 1) // 2 for s in chunks] or [0])
@@ -404,6 +421,14 @@ def reconstruct(received: Sequence[Optional[bytes]], validator_count: int, ctx: 
     """reconstruct.rs:4-9."""
     params = CodeParams.derive_parameters(validator_count, recoverablity_subset_size(validator_count))
     return params.make_encoder(ctx).reconstruct(received)
+
+
+def restore_shards(received: Sequence[Optional[bytes]], validator_count: int,
+                   ctx: Optional[Context] = None) -> List[bytes]:
+    """All ``validator_count`` shards from the received ones (:meth:`ReedSolomon.restore_shards`),
+    with the code :func:`reconstruct` derives."""
+    params = CodeParams.derive_parameters(validator_count, recoverablity_subset_size(validator_count))
+    return params.make_encoder(ctx).restore_shards(received)
 
 
 # -------------------------------------------------- device-resident batch ----
@@ -442,6 +467,17 @@ def reconstruct_codewords_batch_dev(params: CodeParams, d_shards: int, shard_len
     _raise(lib().np_reconstruct_codewords_batch_dev(ctx.handle, C.byref(params._c()), d_shards, shard_len,
                                                     batch_stride, d_present, batch, d_out, out_stride,
                                                     d_status or None, stream or None))
+
+
+def restore_shards_batch_dev(params: CodeParams, d_shards: int, shard_len: int, batch_stride: int, d_present: int,
+                             batch: int, ctx: Optional[Context] = None, stream: int = 0, d_status: int = 0) -> None:
+    """Writes the absent rows below ``wanted_n`` of every payload with at least k
+    present rows into ``d_shards`` (np_restore_shards_batch_dev): the rows of
+    ``encode(reconstruct(received))``, bit-exact with the crate for any received
+    bytes; nothing else is written.  d_status as :func:`reconstruct_batch_dev2`."""
+    ctx = ctx or default_context()
+    _raise(lib().np_restore_shards_batch_dev(ctx.handle, C.byref(params._c()), d_shards, shard_len, batch_stride,
+                                             d_present, batch, d_status or None, stream or None))
 
 
 def payload_errors(params: CodeParams, status_pairs) -> List[Optional[Error]]:
