@@ -140,6 +140,14 @@ int np_rs_reconstruct(np_ctx* ctx, const np_code_params* params, const uint8_t* 
 int np_rs_restore_shards(np_ctx* ctx, const np_code_params* params, const uint8_t* const* shards,
                          const size_t* shard_lens, size_t n_received, uint8_t* const* restored,
                          size_t restored_len);
+/* np_verify_shards_batch_dev for one payload in host memory, staged as
+ * np_rs_restore_shards stages it: shards/shard_lens/n_received as
+ * np_rs_reconstruct (same validation, same errors -- NP_ERR_NEED_MORE_SHARDS is
+ * a return status here; odd lengths zero padded and compared over the padded
+ * row).  *bad_rows: the number of mismatching rows; mismatch: n bytes, 1 for a
+ * mismatching row, or NULL. */
+int np_rs_verify_shards(np_ctx* ctx, const np_code_params* params, const uint8_t* const* shards,
+                        const size_t* shard_lens, size_t n_received, size_t* bad_rows, uint8_t* mismatch);
 /* mod.rs:247-285 ReedSolomon::reconstruct_from_systematic (first k shards, all present). */
 int np_rs_reconstruct_from_systematic(np_ctx* ctx, const np_code_params* params, const uint8_t* const* chunks,
                                       const size_t* chunk_lens, size_t n_chunks, uint8_t* out,
@@ -222,6 +230,45 @@ int np_reconstruct_codewords_batch_dev(np_ctx* ctx, const np_code_params* params
 int np_restore_shards_batch_dev(np_ctx* ctx, const np_code_params* params, uint8_t* d_shards, size_t shard_len,
                                 size_t batch_stride, const uint8_t* d_present, size_t batch,
                                 np_payload_status* d_status, void* stream);
+/* Checks the received shards against their re-encoding (what the
+ * `reed-solomon-erasure` crate calls `verify`, next to its `reconstruct`).
+ * For a payload with >= k present rows let E = ReedSolomon::encode(
+ * ReedSolomon::reconstruct(received)) (mod.rs:117-157 after mod.rs:162-239, the
+ * composition np_restore_shards_batch_dev writes).  Row v MISMATCHES when
+ * v < wanted_n, present[b*n+v] != 0 and the received row differs from E[v] in
+ * any byte; the payload is CONSISTENT when no row mismatches.  Bit-exact with
+ * the reference for any received bytes.
+ *   d_bad_rows  (required) batch entries: the number of mismatching rows, or
+ *               UINT32_MAX for a payload with < k present rows (== 0 never
+ *               holds for an undecodable payload).
+ *   d_mismatch  (may be NULL) batch rows of n bytes, laid out like d_present:
+ *               1 for a mismatching row, 0 for every other entry (rows >=
+ *               wanted_n included); all 0 for an undecodable payload.
+ * d_shards is only read.  Layouts, validation, stream rules, d_status (may be
+ * NULL), the context scratch with its slices and NP_ERR_ALLOC as
+ * np_restore_shards_batch_dev.  The results do not depend on any execution
+ * order: kernels set per-row flags, and the count is taken from the flags.
+ * What the answer means (checked on the CPU reference over (n_wanted, k_wanted)
+ * = (256,86), (600,256), (60,20), (16,8), (1024,512), (10,4);
+ * tests/test_verify_cpu.py):
+ *  - a present systematic row (v < k) never mismatches: the reference decode
+ *    passes present data positions through unchanged, so only present rows in
+ *    [k, wanted_n) are compared;
+ *  - with exactly k present rows the payload is always consistent, random
+ *    bytes included; with >= k+1 present rows of a codeword, changing any one
+ *    symbol of a present row makes at least one row mismatch;
+ *  - the map says which rows differ from the re-encoding, not which rows were
+ *    corrupted: with some systematic rows absent one flipped symbol makes most
+ *    present parity rows mismatch (at (16,8) the flipped row itself did not);
+ *    with every systematic row present exactly the altered parity rows do.
+ * k in {64, 128, 256} (every n >= 2k): the reconstruct, then an encode that
+ * compares the present parity rows with d_shards as it produces them and skips
+ * the transforms of segments that hold none.  Every other shape: the
+ * reconstruct, the ordinary encode into context scratch, and a compare of the
+ * present parity rows. */
+int np_verify_shards_batch_dev(np_ctx* ctx, const np_code_params* params, const uint8_t* d_shards, size_t shard_len,
+                               size_t batch_stride, const uint8_t* d_present, size_t batch, uint32_t* d_bad_rows,
+                               uint8_t* d_mismatch, np_payload_status* d_status, void* stream);
 /* mod.rs:247-285 ReedSolomon::reconstruct_from_systematic for `batch` payloads
  * whose first k shards are all present: d_shards as for np_encode_batch_dev
  * (batch_stride >= k*shard_len, only rows 0..k-1 are read), d_out as for

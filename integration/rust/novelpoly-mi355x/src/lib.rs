@@ -245,6 +245,48 @@ impl ReedSolomon {
 			.collect())
 	}
 
+	/// The indices of the received shards that differ from their row of
+	/// `encode(reconstruct(received_shards))` (odd lengths compared zero
+	/// padded): the rows that differ from the re-encoding, which need not be
+	/// the rows that were altered.  Same errors as `reconstruct`.
+	pub fn mismatched_shards<S: Shard>(&self, received_shards: &[Option<S>]) -> Result<Vec<usize>> {
+		let (ptrs, lens) = shard_views(received_shards);
+		let mut bad = 0usize;
+		let mut flags = vec![0u8; self.params.raw.n.max(1)];
+		check(unsafe {
+			sys::np_rs_verify_shards(
+				self.ctx.raw,
+				&self.params.raw,
+				ptrs.as_ptr(),
+				lens.as_ptr(),
+				ptrs.len(),
+				&mut bad,
+				flags.as_mut_ptr(),
+			)
+		})?;
+		Ok(flags.iter().enumerate().filter(|(_, f)| **f != 0).map(|(i, _)| i).collect())
+	}
+
+	/// Whether every received shard equals its row of
+	/// `encode(reconstruct(received_shards))`; always true with exactly k
+	/// shards.  Same errors as `reconstruct`.
+	pub fn verify<S: Shard>(&self, received_shards: &[Option<S>]) -> Result<bool> {
+		let (ptrs, lens) = shard_views(received_shards);
+		let mut bad = 0usize;
+		check(unsafe {
+			sys::np_rs_verify_shards(
+				self.ctx.raw,
+				&self.params.raw,
+				ptrs.as_ptr(),
+				lens.as_ptr(),
+				ptrs.len(),
+				&mut bad,
+				std::ptr::null_mut(),
+			)
+		})?;
+		Ok(bad == 0)
+	}
+
 	/// mod.rs:247-285: the first k shards, all present.
 	pub fn reconstruct_from_systematic<S: Shard>(&self, chunks: Vec<S>) -> Result<Vec<u8>> {
 		let ptrs: Vec<*const u8> = chunks.iter().map(|c| AsRef::<[u8]>::as_ref(c).as_ptr()).collect();

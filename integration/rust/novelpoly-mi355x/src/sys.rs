@@ -118,6 +118,28 @@ extern "C" {
 		d_status: *mut np_payload_status,
 		stream: *mut c_void,
 	) -> c_int;
+	pub fn np_rs_verify_shards(
+		ctx: *mut np_ctx,
+		params: *const np_code_params,
+		shards: *const *const u8,
+		shard_lens: *const usize,
+		n_received: usize,
+		bad_rows: *mut usize,
+		mismatch: *mut u8,
+	) -> c_int;
+	pub fn np_verify_shards_batch_dev(
+		ctx: *mut np_ctx,
+		params: *const np_code_params,
+		d_shards: *const u8,
+		shard_len: usize,
+		batch_stride: usize,
+		d_present: *const u8,
+		batch: usize,
+		d_bad_rows: *mut u32,
+		d_mismatch: *mut u8,
+		d_status: *mut np_payload_status,
+		stream: *mut c_void,
+	) -> c_int;
 	pub fn np_rs_reconstruct_from_systematic(
 		ctx: *mut np_ctx,
 		params: *const np_code_params,

@@ -629,7 +629,7 @@ int np_debug_bounds_check(np_ctx* c, uint32_t out[8]) {
   return NP_OK;
 }
 
-const char* np_version(void) { return "novelpoly-mi355x 0.3.0 (gfx950)"; }
+const char* np_version(void) { return "novelpoly-mi355x 0.4.0 (gfx950)"; }
 
 size_t np_recoverability_subset_size(size_t n) { return (n ? (n - 1) / 3 : 0) + 1; }
 
@@ -1461,7 +1461,89 @@ hipError_t launch_restore(np_ctx* c, const np_code_params* p, uint8_t* d_shards,
   return hipSuccess;
 }
 
+// np_verify_shards_batch_dev after validation: launch_restore's flow with a
+// compare in place of the store.  Per slice of the batch: the reconstruct into
+// the payload scratch, the flag map zeroed, then either the verify encode that
+// compares the present rows in [k, wanted_n) with d_shards as it produces them
+// or the unchanged encode into scratch rows and the compare of those rows, and
+// the count of the flags.  Shares the restore's scratch, ordering and cap.
+// Caller holds the context lock.
+hipError_t launch_verify(np_ctx* c, const np_code_params* p, const uint8_t* d_shards, size_t shard_len,
+                         size_t bstride, const uint8_t* d_present, size_t batch, uint32_t* d_bad_rows,
+                         uint8_t* d_mismatch, uint32_t* d_status, hipStream_t s) {
+  const uint32_t n = static_cast<uint32_t>(p->n), k = static_cast<uint32_t>(p->k);
+  const uint32_t wanted_n = static_cast<uint32_t>(p->wanted_n);
+  const bool direct = np::masked_encode_supported(n, k);
+  const size_t pay_len = (shard_len / 2) * 2 * p->k;
+  const size_t rows_len = direct ? 0 : p->wanted_n * shard_len;  // scratch shard rows per payload
+  const size_t plan_len = direct ? np::restore_plan_words(n, k) * sizeof(uint32_t) : 0;
+  const size_t own_status = d_status ? 0 : kStatusBytes;
+  const size_t own_flags = d_mismatch ? 0 : p->n;
+  size_t per = c->restore_cap / std::max(pay_len, rows_len);  // as launch_restore
+  per = per >= 8 ? per & ~size_t(7) : std::max<size_t>(1, per);
+  for (size_t b0 = 0; b0 < batch; b0 += per) {
+    const size_t cnt = std::min(per, batch - b0);
+    const size_t o_rows = align256(cnt * pay_len), o_plan = o_rows + align256(cnt * rows_len);
+    const size_t o_status = o_plan + align256(cnt * plan_len), o_flags = o_status + align256(cnt * own_status);
+    uint8_t* scr = nullptr;
+    hipError_t e = restore_scratch(c, o_flags + align256(cnt * own_flags), s, &scr);
+    if (e != hipSuccess) return e;
+    const uint8_t* shards = d_shards + b0 * bstride;
+    uint8_t* flags = d_mismatch ? d_mismatch + b0 * p->n : scr + o_flags;
+    np::ReconstructArgs a{};
+    a.shards = shards;
+    a.shard_len = shard_len;
+    a.batch_stride = bstride;
+    a.present = d_present + b0 * p->n;
+    a.locators = nullptr;  // computed on the device
+    a.batch = cnt;
+    a.n = n;
+    a.k = k;
+    a.out = scr;
+    a.out_stride = pay_len;
+    a.status = d_status ? d_status + 2 * b0 : reinterpret_cast<uint32_t*>(scr + o_status);
+    e = launch_reconstruct(c, a, s);
+    if (e == hipSuccess) e = HIP(hipMemsetAsync(flags, 0, cnt * p->n, s));
+    if (e == hipSuccess && wanted_n > k) {
+      if (direct) {
+        uint32_t* plan = reinterpret_cast<uint32_t*>(scr + o_plan);
+        e = HIP(np::launch_verify_plan(a.present, a.status, n, k, wanted_n, cnt, plan, s));
+        // (EncodeArgs names the rows as the encode's output; the verify encode only reads them)
+        if (e == hipSuccess)
+          e = HIP(np::launch_encode_verify(
+              c->T, enc_args(p, scr, pay_len, pay_len, cnt, const_cast<uint8_t*>(shards), bstride), plan, flags, s));
+      } else {
+        uint8_t* rows = scr + o_rows;
+        e = launch_encode(c, enc_args(p, scr, pay_len, pay_len, cnt, rows, rows_len), s);
+        if (e == hipSuccess)
+          e = HIP(np::launch_compare_present_rows(rows, rows_len, shards, bstride, shard_len, a.present, a.status, n,
+                                                  k, wanted_n, cnt, flags, s));
+      }
+    }
+    if (e == hipSuccess) e = HIP(np::launch_verify_summary(flags, a.status, n, cnt, d_bad_rows + b0, s));
+    if (e != hipSuccess) return e;
+    c->restore_used = true;
+    e = HIP(hipEventRecord(c->restore_done, s));
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 }  // namespace
+
+int np_verify_shards_batch_dev(np_ctx* c, const np_code_params* p, const uint8_t* d_shards, size_t shard_len,
+                               size_t bstride, const uint8_t* d_present, size_t batch, uint32_t* d_bad_rows,
+                               uint8_t* d_mismatch, np_payload_status* d_status, void* stream) {
+  if (!c) return fail(NP_ERR_INVALID_ARGUMENT);
+  int st = check_params(p);
+  if (st) return st;
+  if (shard_len == 0 || (shard_len & 1)) return fail(NP_ERR_EMPTY_SHARD);
+  if (!d_shards || !d_present || !d_bad_rows || bstride < p->n * shard_len) return fail(NP_ERR_INVALID_ARGUMENT);
+  std::lock_guard<std::mutex> g(c->mu);  // context scratch
+  (void)hipSetDevice(c->device);
+  return dev_err(launch_verify(c, p, d_shards, shard_len, bstride, d_present, batch, d_bad_rows, d_mismatch,
+                               reinterpret_cast<uint32_t*>(d_status), pick(c, stream)));
+}
 
 int np_restore_shards_batch_dev(np_ctx* c, const np_code_params* p, uint8_t* d_shards, size_t shard_len,
                                 size_t bstride, const uint8_t* d_present, size_t batch, np_payload_status* d_status,
@@ -1665,6 +1747,69 @@ int np_rs_restore_shards(np_ctx* c, const np_code_params* p, const uint8_t* cons
   if (e != hipSuccess) return dev_err(e);
   for (size_t i = 0; i < p->wanted_n; ++i)
     if (!present[i] && restored[i]) std::memcpy(restored[i], stage + i * sl, sl);
+  return NP_OK;
+}
+
+int np_rs_verify_shards(np_ctx* c, const np_code_params* p, const uint8_t* const* shards, const size_t* lens,
+                        size_t n_received, size_t* bad_rows, uint8_t* mismatch) {
+  // validation as np_rs_reconstruct (mod.rs:163-214)
+  if (!c || !p || !bad_rows || (n_received && (!shards || !lens))) return fail(NP_ERR_INVALID_ARGUMENT);
+  if (!is_pow2(p->n) && !is_pow2(p->k)) return fail(NP_ERR_PARAMETER_MUST_BE_POWER_OF_2, p->n, p->k);
+  const size_t n = p->n, k = p->k;
+  std::vector<uint8_t> present(n, 0);
+  size_t have = 0;
+  for (size_t i = 0; i < n && i < n_received; ++i) {
+    present[i] = shards[i] ? 1 : 0;
+    have += present[i];
+  }
+  if (have < k) return fail(NP_ERR_NEED_MORE_SHARDS, have, k, n);
+  size_t first = 0;
+  while (!present[first]) ++first;
+  const size_t syms = (lens[first] + 1) / 2;
+  if (syms == 0) return fail(NP_ERR_EMPTY_SHARD);
+  for (size_t i = first + 1; i < n; ++i)
+    if (present[i] && (lens[i] + 1) / 2 != syms) return fail(NP_ERR_INCONSISTENT_SHARD_LENGTHS, syms, (lens[i] + 1) / 2);
+  int st = check_params(p);
+  if (st) return st;
+  const size_t sl = 2 * syms;
+  std::lock_guard<std::mutex> g(c->mu);
+  (void)hipSetDevice(c->device);
+  // the count, then (256 bytes on) the n flags
+  const size_t o_map = 256, res_bytes = o_map + n;
+  hipError_t e = HIP(c->h_in.ensure(n * sl));
+  if (e == hipSuccess) e = HIP(c->d_in.ensure(n * sl));
+  if (e == hipSuccess) e = HIP(c->d_present.ensure(n));
+  if (e == hipSuccess) e = HIP(c->h_pres.ensure(n));
+  if (e == hipSuccess) e = HIP(c->d_out.ensure(res_bytes));
+  if (e == hipSuccess) e = HIP(c->h_out.ensure(res_bytes));
+  if (e != hipSuccess) return dev_err(e);
+  std::memcpy(c->h_pres.p, present.data(), n);
+  uint8_t* stage = c->h_in.as<uint8_t>();
+  for (size_t i = 0; i < n; ++i) {
+    uint8_t* row = stage + i * sl;
+    if (present[i]) {
+      std::memcpy(row, shards[i], lens[i]);
+      if (lens[i] < sl) std::memset(row + lens[i], 0, sl - lens[i]);  // WrappedShard zero pad
+    } else {
+      std::memset(row, 0, sl);
+    }
+  }
+  hipStream_t s = c->stream;
+  uint8_t* d_res = c->d_out.as<uint8_t>();
+  e = HIP(hipMemcpyAsync(c->d_in.p, stage, n * sl, hipMemcpyHostToDevice, s));
+  if (e == hipSuccess) e = HIP(hipMemcpyAsync(c->d_present.p, c->h_pres.p, n, hipMemcpyHostToDevice, s));
+  if (e == hipSuccess)
+    e = launch_verify(c, p, c->d_in.as<uint8_t>(), sl, n * sl, c->d_present.as<uint8_t>(), 1,
+                      reinterpret_cast<uint32_t*>(d_res), d_res + o_map, nullptr, s);
+  if (e == hipSuccess) e = HIP(hipMemcpyAsync(c->h_out.p, d_res, res_bytes, hipMemcpyDeviceToHost, s));
+  if (e == hipSuccess) e = HIP(hipStreamSynchronize(s));
+  if (e != hipSuccess) return dev_err(e);
+  const uint8_t* res = c->h_out.as<uint8_t>();
+  uint32_t count = 0;
+  std::memcpy(&count, res, sizeof(count));
+  if (count == UINT32_MAX) return fail(NP_ERR_NEED_MORE_SHARDS, have, k, n);  // (caught above: have >= k decodes)
+  *bad_rows = count;
+  if (mismatch) std::memcpy(mismatch, res + o_map, n);
   return NP_OK;
 }
 

@@ -1791,6 +1791,7 @@ hipError_t launch_reconstruct_fast(const DevTables& T, const ReconstructArgs& a,
 
 namespace {
 hipError_t configure_masked_kernels();  // below, with the masked encode's launchers
+hipError_t configure_verify_kernels();  // at the end of the file, with the verify encode
 }
 
 hipError_t configure_fast_kernels() {
@@ -1819,6 +1820,7 @@ hipError_t configure_fast_kernels() {
   set(reinterpret_cast<const void*>(&k_reconstruct_fast<256, 8, 2>), reconstruct_lds_bytes<256, 8>());
   set(reinterpret_cast<const void*>(&k_reconstruct_fast<256, 8, 8>), reconstruct_lds_bytes<256, 8>());
   if (e == hipSuccess) e = configure_masked_kernels();
+  if (e == hipSuccess) e = configure_verify_kernels();
   return e;
 }
 
@@ -1868,6 +1870,283 @@ hipError_t launch_encode_masked(const DevTables& T, const EncodeArgs& a, const u
     case 64: return launch_encode_masked_k<64>(T, a, plan, s);
     case 128: return launch_encode_masked_k<128>(T, a, plan, s);
     case 256: return launch_encode_masked_k<256>(T, a, plan, s);
+    default: return hipErrorNotSupported;
+  }
+}
+
+// --------------------------------------------------------- verify encode ----
+// np_verify_shards_batch_dev: k_encode_masked's flow on the reconstructed
+// payload with a compare in place of the store.  The plan (k_verify_plan) marks
+// the present rows in [K, wanted_n) of a decoded payload; a wave re-encodes its
+// 16 rows of a shift, reads the received bytes of the marked ones and sets the
+// row's flag when any of the tile's columns differs.  Nothing else is written:
+// a.shards is only read.  Segment 0 is never marked (a present systematic row
+// equals its re-encoding), so a payload with no marked row exits before the
+// tile load; the skipped shifts, the unstaged tables, the `rows` mask of the cq
+// levels and kShift3Own are the masked encode's.
+// The last kernel of this file: every older kernel's assembly stays what it was.
+namespace {
+
+// Received rows a wave loads before it compares them.  A workgroup's waves
+// reach the compare together, so nothing else hides the loads' latency: 8 in
+// flight measured 1 % below 4 on the whole call at config 3;
+// 16 spill (28-40 bytes of scratch per lane).
+constexpr int kVerifyGroup = 8;
+
+// XOR of the received 4 columns of this lane with the re-encoded ones, for
+// lanes and columns below ncols (others: 0).
+__device__ __forceinline__ uint32_t diff4(const uint8_t* rowp, uint2 v, uint32_t lane, uint32_t ncols) {
+  uint32_t d = 0;
+  if (4 * lane + 4 <= ncols) {  // lanes with all four columns
+    const uint2 r = *reinterpret_cast<const uint2*>(rowp + 8u * lane);
+    d = (r.x ^ v.x) | (r.y ^ v.y);
+  } else {
+    const uint32_t w[2] = {v.x, v.y};
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (4 * lane + i < ncols) {
+        const uint32_t r = *reinterpret_cast<const uint16_t*>(rowp + 8u * lane + 2 * i);
+        d |= r ^ ((w[i >> 1] >> (16 * (i & 1))) & 0xffffu);
+      }
+  }
+  return d;
+}
+
+// The rows of `mask` (wave-uniform) among row0..row0+15: flag[row0 + p] = 1
+// when the received row differs from cq_row(L[p], H[p]) in a column of this
+// tile.  Full tiles load kVerifyGroup rows at a time through per-row
+// descriptors of size 0 for unmarked rows (no branch, no traffic; as
+// issue_rows_c): loading all 16 ahead of the cq levels, or after them, spills.
+__device__ __forceinline__ void compare_rows_masked(const uint8_t* in, size_t shard_len, uint32_t row0, uint32_t mask,
+                                                    const uint32_t (&L)[16], const uint32_t (&H)[16], uint32_t lane,
+                                                    uint32_t ncols, bool full, uint8_t* flag) {
+  if (mask == 0) return;
+  if (full) {
+#pragma unroll
+    for (int p0 = 0; p0 < 16; p0 += kVerifyGroup) {
+      if (((mask >> p0) & ((1u << kVerifyGroup) - 1u)) == 0) continue;
+      u32x2 r[kVerifyGroup];
+#pragma unroll
+      for (int q = 0; q < kVerifyGroup; ++q) {
+        const int p = p0 + q;
+        const uint8_t* rowp = in + static_cast<size_t>(row0 + p) * shard_len;
+        if ((mask >> p) & 1u) NP_BNOTE(rowp + 8u * lane, 8, kBkShards);
+        const __amdgpu_buffer_rsrc_t rs = buf_rsrc(rowp, ((mask >> p) & 1u) ? 512u : 0u);
+        r[q] = __builtin_amdgcn_raw_buffer_load_b64(rs, 8u * lane, 0, 2);  // read once: streaming
+      }
+#pragma unroll
+      for (int q = 0; q < kVerifyGroup; ++q) {
+        const int p = p0 + q;
+        if ((mask >> p) & 1u) {
+          const uint2 v = cq_row(L[p], H[p]);
+          const bool any = __builtin_amdgcn_ballot_w64(((r[q].x ^ v.x) | (r[q].y ^ v.y)) != 0) != 0;
+          NP_BNOTE(flag + (row0 + p), 1, kBkOut);
+          if (any && lane == 0) flag[row0 + p] = 1;
+        }
+      }
+    }
+  } else {
+#pragma unroll
+    for (int p = 0; p < 16; ++p)
+      if ((mask >> p) & 1u) {
+        const uint8_t* rowp = in + static_cast<size_t>(row0 + p) * shard_len;
+        NP_BNOTE(rowp, 2u * ncols, kBkShards);
+        const uint32_t d = diff4(rowp, cq_row(L[p], H[p]), lane, ncols);
+        const bool any = __builtin_amdgcn_ballot_w64(d != 0) != 0;
+        NP_BNOTE(flag + (row0 + p), 1, kBkOut);
+        if (any && lane == 0) flag[row0 + p] = 1;
+      }
+  }
+}
+
+template <int K>
+__global__ __launch_bounds__(4 * K) __attribute__((amdgpu_waves_per_eu(4))) void k_encode_verify(
+    DevTables T, EncodeArgs a, uint32_t nchunks, uint32_t tiles, const uint32_t* plan, uint8_t* flags) {
+  using G = Geo<K>;
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  uint8_t* tile = smem;
+  uint32_t* VP = reinterpret_cast<uint32_t*>(smem + G::kTileBytes);  // up to 4 staged transforms
+  const uint32_t nshift = a.n / K;
+  const uint32_t segw = static_cast<uint32_t>(restore_seg_words(a.n, K));
+  const uint32_t planw = static_cast<uint32_t>(restore_plan_words(a.n, K));
+#if NP_BOUNDS_CHECK
+  {
+    BoundsSet b = bounds_of_enc(a);  // shards: the received rows, read only
+    b.lo[kBkRecords] = reinterpret_cast<uint64_t>(plan);
+    b.hi[kBkRecords] = b.lo[kBkRecords] + a.batch * planw * 4u;
+    b.lo[kBkOut] = reinterpret_cast<uint64_t>(flags);
+    b.hi[kBkOut] = b.lo[kBkOut] + a.batch * static_cast<uint64_t>(a.n);
+    bounds_arm(b);
+  }
+#endif
+  const TileRef tr = tile_of(blockIdx.x, tiles, (a.batch & 7u) == 0);
+  const uint32_t pb = tr.pb, tl = tr.tl;
+  NP_BNOTE(plan + static_cast<size_t>(pb) * planw, 4u * planw, kBkRecords);
+  const cpool_t seg = (cpool_t)(plan) + static_cast<size_t>(pb) * planw;
+  const cpool_t rowbits = seg + segw;
+  const uint32_t first = next_segment(seg, 1, nshift);  // the first shift to run
+  if (first == nshift) return;                          // no row to compare (or NeedMoreShards)
+  const uint32_t ch0 = tl * kTile;
+  const uint32_t ncols = min(static_cast<uint32_t>(kTile), nchunks - ch0);
+  const uint8_t* pay = a.payloads + static_cast<size_t>(pb) * a.payload_stride;
+  const uint8_t* in = a.shards + static_cast<size_t>(pb) * a.batch_stride + 2 * static_cast<size_t>(ch0);
+  uint8_t* flag = flags + static_cast<size_t>(pb) * a.n;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, g = uniform(tid >> 6);
+  const bool full = ncols == kTile && rows_vec_ok(a.shards, a.batch_stride, a.shard_len);
+
+  // ---- tile load (as k_encode_fast)
+  {
+    const uint32_t c0 = tid / G::Q, m0 = tid % G::Q;
+    const uint32_t base = col_base<K>(c0) ^ (8u * m0);
+    const size_t gbase = static_cast<size_t>(ch0 + c0) * 2 * K + 8u * m0;
+    const bool fast = out_vec_ok(pay, 0) && static_cast<size_t>(ch0 + kTile) * 2 * K <= a.payload_len;
+    if (fast) {
+      uint2 v[16];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) v[i] = load_once(pay + gbase + static_cast<size_t>(i) * 32 * K);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) *reinterpret_cast<uint2*>(tile + (base ^ col_base_c<K>(16u * i))) = v[i];
+    } else {
+#pragma unroll 1
+      for (uint32_t i = 0; i < 16; ++i) {
+        const size_t g0 = gbase + static_cast<size_t>(i) * 32 * K;
+        uint32_t w[2] = {0, 0};
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (g0 + e < a.payload_len) w[e >> 2] |= static_cast<uint32_t>(*NP_BCHK(pay + (g0 + e), 1, kBkPayloads)) << (8 * (e & 3));
+        *reinterpret_cast<uint2*>(tile + (base ^ col_base_c<K>(16u * i))) = make_uint2(w[0], w[1]);
+      }
+    }
+  }
+  // n <= 4K: one table buffer per transform that runs; otherwise two buffers
+  // alternate, each shift staging the next one that runs
+  const bool resident = nshift <= 4;
+  stage_vpools<K, G::kThreads>(T, 0, VP, true);  // inverse transform, index 0
+  if (resident) {
+    for (uint32_t sh = first; sh < nshift; sh = next_segment(seg, sh + 1, nshift))
+      stage_vpools<K, G::kThreads>(T, sh * K, VP + sh * G::kVPWords, true, enc_conv_u<K>(sh));
+  } else {
+    stage_vpools<K, G::kThreads>(T, first * K, VP + G::kVPWords, uniform_b(first < 4), enc_conv_u<K>(first));
+  }
+  __syncthreads();
+
+  const uint32_t cqb = col_base<K>(4 * lane) ^ (32u * g);  // blocks 4g..4g+3 of columns 4l..4l+3
+  // ---- cq pass: inverse levels 0..3
+  {
+    uint32_t CL[16], CH[16];
+    cq_read<K>(tile, cqb, CL, CH);
+    tower_convert(T, CL, CH);  // transforms run in tower coordinates
+    cq_levels<K, true, true, 0, false, kEncPrioCq>(T, VP, 0, g, CL, CH);
+    // the quad items overlay payload blocks that other waves read: wait for
+    // every wave's cq_read
+    __syncthreads();
+    cq_write_q(tile, g, lane, CL, CH);
+  }
+  __syncthreads();
+  // ---- high layout: inverse levels 4.. -> coefficients M
+  uint32_t ML[16], MH[16];
+  hi_read_q<K>(tile, g, lane, ML, MH);
+  hi_levels<K, true, true, 0, 0, kEncPrio>(T, VP, 0, ML, MH);
+#pragma unroll
+  for (int q = 0; q < 16; ++q) asm volatile("" : "+v"(ML[q]), "+v"(MH[q]));  // materialise M once
+
+  // top-level products of shift 1, then of shifts 1 ^ 2 (fwd_top); zero, so that
+  // a shift 2 without shift 1 accumulates into defined values (which nobody reads)
+  uint32_t PL[8] = {}, PH[8] = {};
+  uint32_t slot = 1;  // !resident: the table buffer of the shift that runs
+  // shift sh; nxt: the next shift that runs (nshift: none)
+  auto shift = [&](auto shc, uint32_t sh, uint32_t nxt) __attribute__((always_inline)) {
+    constexpr int SH = decltype(shc)::value;
+    constexpr int SHC = SH == kShift3Own ? 3 : SH;
+    const uint32_t index = sh * K;
+    uint32_t XL[16], XH[16];
+    const uint32_t* vp = VP + (resident ? sh : slot) * G::kVPWords;
+    if constexpr (SH == kShift3Own) {
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        XL[q] = ML[q];
+        XH[q] = MH[q];
+      }
+      fwd_top<K, 0, 0>(T, vp, index, XL, XH, PL, PH);
+      hi_levels<K, false, false, 1, 0, kEncPrio>(T, vp, index, XL, XH);
+    } else {
+      shift_hi<K, SH>(T, vp, index, ML, MH, XL, XH, PL, PH);
+    }
+    __syncthreads();  // the previous cq pass is done with the tile and with the other table buffer
+    if (!resident && nxt < nshift)
+      stage_vpools<K, G::kThreads>(T, nxt * K, VP + (slot ^ 1u) * G::kVPWords, uniform_b(nxt < 4),
+                                   enc_conv_u<K>(nxt));
+    hi_write_q<K>(tile, g, lane, XL, XH);
+    __syncthreads();
+    cq_read_q(tile, g, lane, XL, XH);
+    const uint32_t mask = restore_mask16(rowbits, index + 16 * g);
+    shift_cq_rows<K, SHC>(T, vp, index, g, XL, XH, mask);
+    compare_rows_masked(in, a.shard_len, index + 16 * g, mask, XL, XH, lane, ncols, full, flag);
+    slot ^= 1u;
+  };
+  const bool own3 = ((seg[0] >> 1) & 3u) != 3u;  // shift 1 or 2 skipped
+  // cur: the next shift to run; nshift (2 at n = 2K: not "shift 2") when none is left
+  uint32_t cur = first;
+  if (cur == 1) {
+    const uint32_t nxt = next_segment(seg, 2, nshift);
+    shift(Int<1>{}, 1, nxt);
+    cur = nxt;
+  }
+  if (cur == 2 && cur < nshift) {
+    const uint32_t nxt = next_segment(seg, 3, nshift);
+    shift(Int<2>{}, 2, nxt);
+    cur = nxt;
+  }
+  if (cur == 3 && cur < nshift) {
+    const uint32_t nxt = next_segment(seg, 4, nshift);
+    if (own3)
+      shift(Int<kShift3Own>{}, 3, nxt);
+    else
+      shift(Int<3>{}, 3, nxt);
+    cur = nxt;
+  }
+#pragma unroll 1
+  while (cur < nshift) {
+    const uint32_t nxt = next_segment(seg, cur + 1, nshift);
+    shift(Int<0>{}, cur, nxt);
+    cur = nxt;
+  }
+}
+
+template <int K>
+hipError_t launch_encode_verify_k(const DevTables& T, const EncodeArgs& a, const uint32_t* plan, uint8_t* flags,
+                                  hipStream_t s) {
+  const size_t nchunks = (a.payload_len + 2 * a.k - 1) / (2 * a.k);
+  if (nchunks == 0 || a.batch == 0) return hipSuccess;
+  if (nchunks > 0xffffffffu) return hipErrorInvalidValue;
+  const uint32_t tiles = static_cast<uint32_t>((nchunks + kTile - 1) / kTile);
+  const size_t blocks = a.batch * tiles;
+  if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
+  k_encode_verify<K><<<static_cast<uint32_t>(blocks), Geo<K>::kThreads, encode_lds_bytes<K>(), s>>>(
+      T, a, static_cast<uint32_t>(nchunks), tiles, plan, flags);
+  return hipGetLastError();
+}
+
+hipError_t configure_verify_kernels() {
+  hipError_t e = hipSuccess;
+  auto set = [&](const void* f, size_t bytes) {
+    hipError_t r = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
+    if (r != hipSuccess && e == hipSuccess) e = r;
+  };
+  set(reinterpret_cast<const void*>(&k_encode_verify<64>), encode_lds_bytes<64>());
+  set(reinterpret_cast<const void*>(&k_encode_verify<128>), encode_lds_bytes<128>());
+  set(reinterpret_cast<const void*>(&k_encode_verify<256>), encode_lds_bytes<256>());
+  return e;
+}
+
+}  // namespace
+
+hipError_t launch_encode_verify(const DevTables& T, const EncodeArgs& a, const uint32_t* plan, uint8_t* flags,
+                                hipStream_t s) {
+  switch (a.k) {
+    case 64: return launch_encode_verify_k<64>(T, a, plan, flags, s);
+    case 128: return launch_encode_verify_k<128>(T, a, plan, flags, s);
+    case 256: return launch_encode_verify_k<256>(T, a, plan, flags, s);
     default: return hipErrorNotSupported;
   }
 }

@@ -198,4 +198,27 @@ hipError_t launch_copy_absent_rows(const uint8_t* src, size_t sstride, uint8_t* 
                                    size_t row_bytes, const uint8_t* present, const uint32_t* status, uint32_t n,
                                    uint32_t rows, size_t count, hipStream_t s);
 hipError_t bounds_take_restore(uint32_t out[8]);
+
+// ---- checking shards against their re-encoding (np_verify_shards_batch_dev) ----
+// The plan has the restore plan's layout with another meaning: row bit v set
+// when row v is compared -- present, in [k, wanted_n), and the payload's status
+// OK -- and segment bit q set when segment q holds such a row (bit 0 never).
+// flags: n bytes per payload, zeroed by the caller before the compare; a
+// kernel sets flags[b * n + v] = 1 when row v of payload b differs from the
+// re-encoding and writes nothing else.
+hipError_t launch_verify_plan(const uint8_t* present, const uint32_t* status, uint32_t n, uint32_t k,
+                              uint32_t wanted_n, size_t batch, uint32_t* plan, hipStream_t s);
+// Where masked_encode_supported: the masked encode's flow with a compare of the
+// plan's rows against a.shards (read only) in place of the store.
+hipError_t launch_encode_verify(const DevTables& T, const EncodeArgs& a, const uint32_t* plan, uint8_t* flags,
+                                hipStream_t s);
+// Every other shape: enc[b][v] against recv[b][v] (row_bytes each, any even
+// address) for b < count, k <= v < rows with present[b * n + v] != 0 and
+// status[2 b] == 0.
+hipError_t launch_compare_present_rows(const uint8_t* enc, size_t estride, const uint8_t* recv, size_t rstride,
+                                       size_t row_bytes, const uint8_t* present, const uint32_t* status, uint32_t n,
+                                       uint32_t k, uint32_t rows, size_t count, uint8_t* flags, hipStream_t s);
+// counts[b] = number of set flags of payload b, UINT32_MAX when status[2 b] != 0.
+hipError_t launch_verify_summary(const uint8_t* flags, const uint32_t* status, uint32_t n, size_t batch,
+                                 uint32_t* counts, hipStream_t s);
 }  // namespace np

@@ -74,6 +74,8 @@ def lib() -> C.CDLL:
             "np_reconstruct_codewords_batch_dev": (C.c_int, [vp, P, vp, _sz, _sz, vp, _sz, vp, _sz, vp, vp]),
             "np_restore_shards_batch_dev": (C.c_int, [vp, P, vp, _sz, _sz, vp, _sz, vp, vp]),
             "np_rs_restore_shards": (C.c_int, [vp, P, C.POINTER(vp), C.POINTER(_sz), _sz, C.POINTER(vp), _sz]),
+            "np_verify_shards_batch_dev": (C.c_int, [vp, P, vp, _sz, _sz, vp, _sz, vp, vp, vp, vp]),
+            "np_rs_verify_shards": (C.c_int, [vp, P, C.POINTER(vp), C.POINTER(_sz), _sz, C.POINTER(_sz), vp]),
             "np_error_locator_dev": (C.c_int, [vp, _sz, vp, _sz, vp, vp]),
             "np_reconstruct_from_systematic_batch_dev": (C.c_int, [vp, P, vp, _sz, _sz, _sz, vp, _sz, vp]),
             "np_encode_batch_host": (C.c_int, [vp, P, vp, _sz, _sz, _sz, vp, _sz]),
@@ -400,6 +402,31 @@ class ReedSolomon:
         return [bufs[i].raw[:sl] if i in bufs else WrappedShard(_as_bytes(received[i])).inner
                 for i in range(self.wanted_n)]
 
+    def mismatched_shards(self, received: Sequence[Optional[bytes]]) -> List[int]:
+        """The indices of the received shards that differ from
+        ``encode(reconstruct(received))`` (np_rs_verify_shards; odd lengths are
+        compared zero padded).  They are the rows that differ from the
+        re-encoding, not necessarily the rows that were altered.  Raises as
+        :meth:`reconstruct` does."""
+        ptrs, lens, keep = _shard_arrays(received)
+        bad = _sz(0)
+        flags = C.create_string_buffer(max(1, self.n))
+        _raise(lib().np_rs_verify_shards(self.ctx.handle, C.byref(self._p), ptrs, lens, len(received), C.byref(bad),
+                                         C.cast(flags, C.c_void_p)))
+        rows = [i for i, f in enumerate(flags.raw[: self.n]) if f]
+        assert len(rows) == bad.value
+        return rows
+
+    def verify(self, received: Sequence[Optional[bytes]]) -> bool:
+        """True when every received shard equals its row of
+        ``encode(reconstruct(received))`` (np_rs_verify_shards).  Always true
+        with exactly k shards.  Raises as :meth:`reconstruct` does."""
+        ptrs, lens, keep = _shard_arrays(received)
+        bad = _sz(0)
+        _raise(lib().np_rs_verify_shards(self.ctx.handle, C.byref(self._p), ptrs, lens, len(received), C.byref(bad),
+                                         None))
+        return bad.value == 0
+
     def reconstruct_from_systematic(self, chunks: Sequence[bytes]) -> bytes:
         ptrs, lens, keep = _shard_arrays(chunks)
         maxsyms = max([(len(_as_bytes(s)) + 1) // 2 for s in chunks] or [0])
@@ -429,6 +456,13 @@ def restore_shards(received: Sequence[Optional[bytes]], validator_count: int,
     with the code :func:`reconstruct` derives."""
     params = CodeParams.derive_parameters(validator_count, recoverablity_subset_size(validator_count))
     return params.make_encoder(ctx).restore_shards(received)
+
+
+def verify(received: Sequence[Optional[bytes]], validator_count: int, ctx: Optional[Context] = None) -> bool:
+    """Whether the received shards are consistent (:meth:`ReedSolomon.verify`), with the code
+    :func:`reconstruct` derives."""
+    params = CodeParams.derive_parameters(validator_count, recoverablity_subset_size(validator_count))
+    return params.make_encoder(ctx).verify(received)
 
 
 # -------------------------------------------------- device-resident batch ----
@@ -478,6 +512,22 @@ def restore_shards_batch_dev(params: CodeParams, d_shards: int, shard_len: int, 
     ctx = ctx or default_context()
     _raise(lib().np_restore_shards_batch_dev(ctx.handle, C.byref(params._c()), d_shards, shard_len, batch_stride,
                                              d_present, batch, d_status or None, stream or None))
+
+
+def verify_shards_batch_dev(params: CodeParams, d_shards: int, shard_len: int, batch_stride: int, d_present: int,
+                            batch: int, d_bad_rows: int, ctx: Optional[Context] = None, stream: int = 0,
+                            d_mismatch: int = 0, d_status: int = 0) -> None:
+    """Compares every present row below ``wanted_n`` with its row of
+    ``encode(reconstruct(received))`` (np_verify_shards_batch_dev), bit-exact
+    with the crate for any received bytes; ``d_shards`` is only read.
+    ``d_bad_rows``: one uint32 per payload, the number of mismatching rows, or
+    0xFFFFFFFF for a payload with fewer than k present rows.  ``d_mismatch``
+    (optional): ``batch x n`` bytes, 1 for a mismatching row.  d_status as
+    :func:`reconstruct_batch_dev2`."""
+    ctx = ctx or default_context()
+    _raise(lib().np_verify_shards_batch_dev(ctx.handle, C.byref(params._c()), d_shards, shard_len, batch_stride,
+                                            d_present, batch, d_bad_rows, d_mismatch or None, d_status or None,
+                                            stream or None))
 
 
 def payload_errors(params: CodeParams, status_pairs) -> List[Optional[Error]]:

@@ -1,0 +1,308 @@
+"""np_verify_shards_batch_dev / np_rs_verify_shards: a present row below
+wanted_n mismatches when it differs from its row of the reference's
+ReedSolomon::encode(ReedSolomon::reconstruct(received)) (mod.rs:117-157 after
+mod.rs:162-239).  The per-payload counts and the optional flag map equal the
+oracle's for any received bytes, the shard buffer is only read, and nothing
+around the results is written.
+
+Each shape is one batch whose payloads carry the patterns of `_patterns`; the
+oracle's answer is computed once per shape and shared by the variants (with and
+without d_status, with and without d_mismatch, d_shards at offsets 0 and 2 of
+its allocation).  Direct shapes (k in {64, 128, 256}) run the verify encode,
+the others the encode into scratch and the compare of the present rows."""
+import functools
+
+import numpy as np
+import pytest
+
+import novelpoly_amd as npa
+
+pytestmark = pytest.mark.gpu
+
+FILL = 0x5A
+GUARD = 0xA5
+SL = 2 * 300  # one full 256-column tile plus a partial one
+UNDECODABLE = 0xFFFFFFFF
+
+# (n_wanted, k_wanted, shard_len)
+DIRECT = [(256, 86, SL), (512, 128, SL), (1024, 342, SL),  # n = 4k
+          (600, 256, SL),     # n1024 k256, wanted_n inside segment 2
+          (512, 256, SL),     # n = 2k
+          (512, 64, SL), (2048, 256, SL),  # n = 8k: the runtime shift loop
+          (700, 234, SL)]     # n1024 k128, partial segment 5
+# k <= 32 (small, generic), k = 512, k = 1024 (resident), k = 2048 (big), k = 4096 (huge)
+FALLBACK = [(60, 20, SL), (16, 8, SL), (1024, 20, SL), (1024, 512, SL), (4096, 1366, 2 * 260),
+            (7000, 2334, 2 * 260), (16384, 5462, 2 * 70)]
+LARGE = {(4096, 1366), (7000, 2334), (16384, 5462)}  # patterns 1, 2, 3, 10, 11 only
+
+
+def _dev(a):
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _host(t):
+    import torch
+
+    torch.cuda.synchronize()
+    return t.cpu().numpy()
+
+
+def _codeword(oracle, rng, n, k, wn, sl):
+    plen = (sl // 2) * 2 * k - 3
+    st, shards = oracle.encode(rng.integers(0, 256, plen, dtype=np.uint8).tobytes(), n, k, wn)
+    assert st == 0 and len(shards[0]) == sl
+    rows = np.full((n, sl), FILL, np.uint8)
+    rows[:wn] = np.stack([np.frombuffer(s, np.uint8) for s in shards])
+    return rows
+
+
+def _flip(rows, v, sym, rng):
+    """One bit of symbol `sym` of row v."""
+    rows[v, 2 * sym + int(rng.integers(0, 2))] ^= np.uint8(1 << int(rng.integers(0, 8)))
+
+
+def _patterns(oracle, rng, n, k, wn, sl, large):
+    """[(name, rows n x sl, present n, exact)] -- rows >= wanted_n are never
+    present; exact: the mismatching rows when the pattern fixes them, else None."""
+    syms = sl // 2
+
+    def rand_rows():
+        return rng.integers(0, 256, (n, sl), dtype=np.uint8)
+
+    def pres_without(absent):
+        p = np.zeros(n, np.uint8)
+        p[:wn] = 1
+        p[np.asarray(absent, dtype=np.int64)] = 0
+        return p
+
+    def parity(p):  # present parity rows
+        return np.flatnonzero(p[k:wn]) + k
+
+    out = []
+    code = _codeword(oracle, rng, n, k, wn, sl)
+    pres1 = pres_without(rng.choice(wn, min((n - k) // 2, wn - k - 1), replace=False))
+    # 1: a codeword, min((n - k) / 2, wanted_n - k - 1) random rows absent
+    out.append(("codeword", code, pres1, []))
+    # 2: one bit of the last symbol (a partial-tile column) of a present parity row
+    rows = code.copy()
+    _flip(rows, int(rng.choice(parity(pres1))), syms - 1, rng)
+    out.append(("last-symbol", rows, pres1, None))
+    # 3: one bit of symbol 0 of the first present parity row
+    rows = code.copy()
+    _flip(rows, int(parity(pres1)[0]), 0, rng)
+    out.append(("first-symbol", rows, pres1, None))
+    if not large:
+        # 4: symbols 255 and 256 (the tile boundary) of two different present parity rows
+        rows = code.copy()
+        two = rng.choice(parity(pres1), 2, replace=False)
+        _flip(rows, int(two[0]), 255, rng)
+        _flip(rows, int(two[1]), 256, rng)
+        out.append(("tile-boundary", rows, pres1, None))
+        # 5: copy mode -- every systematic row, half of the parity rows, two of them altered
+        rows = code.copy()
+        pres = pres_without(k + rng.choice(wn - k, (wn - k) // 2, replace=False))
+        two = rng.choice(parity(pres), 2, replace=False)
+        _flip(rows, int(two[0]), int(rng.integers(0, syms)), rng)
+        _flip(rows, int(two[1]), int(rng.integers(0, syms)), rng)
+        out.append(("copy-mode", rows, pres, sorted(int(v) for v in two)))
+        # 6: a present systematic row altered while other systematic rows are absent
+        rows = code.copy()
+        gone = rng.choice(k, min(3, k - 1), replace=False)
+        pres = pres_without(gone)
+        _flip(rows, int(rng.choice(np.setdiff1d(np.arange(k), gone))), int(rng.integers(0, syms)), rng)
+        out.append(("systematic-flip", rows, pres, None))
+        # 7: present parity rows confined to single segments, one row of each altered
+        for qs in {4: [[3], [1, 3]], 8: [[5], [4, 7]]}.get(n // k, []):
+            rows = code.copy()
+            pres = np.zeros(n, np.uint8)
+            pres[:k] = 1
+            hit = []
+            for q in qs:
+                seg = np.arange(q * k, min((q + 1) * k, wn))
+                pres[seg] = 1
+                if len(seg):
+                    hit.append(int(rng.choice(seg)))
+                    _flip(rows, hit[-1], int(rng.integers(0, syms)), rng)
+            out.append(("segments-" + "+".join(map(str, qs)), rows, pres, sorted(hit)))
+        # 8: random bytes, exactly k rows present: always consistent
+        out.append(("random-exactly-k", rand_rows(), pres_without(rng.choice(wn, wn - k, replace=False)), []))
+        # 9: random bytes, more than k rows present
+        out.append(("random", rand_rows(), pres1, None))
+    # 10: k - 1 rows present: NeedMoreShards
+    out.append(("k-1", rand_rows(), pres_without(rng.choice(wn, wn - k + 1, replace=False)), None))
+    # 11: every row of a codeword
+    out.append(("all-present", code, pres_without([]), []))
+    return out
+
+
+def _expected_flags(oracle, rows, pres, n, k, wn, sl):
+    """n flags (1: row v < wanted_n is present and differs from the
+    re-encoding), or None for NeedMoreShards."""
+    recv = [rows[v].tobytes() if pres[v] else None for v in range(n)]
+    st, pay = oracle.reconstruct(recv, n, k)
+    if st:
+        assert st == npa.NeedMoreShards.code
+        return None
+    assert len(pay) == (sl // 2) * 2 * k
+    st, enc = oracle.encode(pay, n, k, wn)
+    assert st == 0 and len(enc[0]) == sl
+    flags = np.zeros(n, np.uint8)
+    for v in range(wn):
+        if pres[v] and enc[v] != recv[v]:
+            flags[v] = 1
+    return flags
+
+
+@functools.lru_cache(maxsize=None)
+def _shape_case(oracle, nw, kw, sl):
+    """The shape's batch and the oracle's answer, computed once (read only)."""
+    p = npa.CodeParams.derive_parameters(nw, kw)
+    n, k, wn = p.n(), p.k(), p.wanted_n
+    rng = np.random.default_rng(1000 * nw + kw + sl)
+    pats = _patterns(oracle, rng, n, k, wn, sl, (nw, kw) in LARGE)
+    flags = np.zeros((len(pats), n), np.uint8)
+    counts, status = [], []
+    for b, (name, rows, pr, exact) in enumerate(pats):
+        exp = _expected_flags(oracle, rows, pr, n, k, wn, sl)
+        if exp is None:
+            assert name == "k-1"
+            counts.append(UNDECODABLE)
+            status.append((npa.NeedMoreShards.code, int(pr.sum())))
+            continue
+        assert name != "k-1"
+        if exact is not None:  # the patterns whose answer the semantics fix
+            assert np.flatnonzero(exp).tolist() == exact, (name, np.flatnonzero(exp).tolist(), exact)
+        elif name != "random":
+            assert exp.any(), name  # an altered symbol with > k rows present shows
+        assert not exp[:k].any(), name  # systematic rows never mismatch
+        flags[b] = exp
+        counts.append(int(exp.sum()))
+        status.append((0, int(pr.sum())))
+    for a in (flags,):
+        a.setflags(write=False)
+    return p, pats, flags, np.asarray(counts, np.uint32), status
+
+
+def _run_shape(gpu, oracle, nw, kw, sl):
+    import torch
+
+    p, pats, want_flags, want_counts, status = _shape_case(oracle, nw, kw, sl)
+    n, k = p.n(), p.k()
+    batch = len(pats)
+    pres = np.stack([pr for _, _, pr, _ in pats])
+    dpres = _dev(pres)
+    s = torch.cuda.current_stream().cuda_stream
+    for offset, slack in ((0, 64), (2, 2)):  # offset 2, stride n * sl + 2: rows at any even address
+        stride = n * sl + slack
+        before = np.full(offset + batch * stride + 64, FILL, np.uint8)
+        for b, (name, rows, pr, _) in enumerate(pats):
+            view = before[offset + b * stride: offset + b * stride + n * sl].reshape(n, sl)
+            view[pr != 0] = rows[pr != 0]
+        buf = _dev(before)
+        for with_status in (True, False):
+            for with_map in (True, False):
+                tag = f"offset {offset}, status {with_status}, map {with_map}"
+                st_d = torch.full((batch, 2), -1, dtype=torch.int32, device="cuda")
+                cnt_d = torch.full((64 + 4 * batch + 64,), GUARD, dtype=torch.uint8, device="cuda")
+                map_d = torch.full((64 + batch * n + 64,), GUARD, dtype=torch.uint8, device="cuda")
+                npa.verify_shards_batch_dev(p, buf.data_ptr() + offset, sl, stride, dpres.data_ptr(), batch,
+                                            cnt_d.data_ptr() + 64, ctx=gpu, stream=s,
+                                            d_mismatch=map_d.data_ptr() + 64 if with_map else 0,
+                                            d_status=st_d.data_ptr() if with_status else 0)
+                cnt, mp = _host(cnt_d), _host(map_d)
+                assert (cnt[:64] == GUARD).all() and (cnt[-64:] == GUARD).all(), tag
+                got_counts = cnt[64:-64].copy().view(np.uint32)
+                print(f"{nw},{kw} {tag}: counts {got_counts.tolist()} want {want_counts.tolist()}")
+                assert got_counts.tolist() == want_counts.tolist(), tag
+                if with_map:
+                    assert (mp[:64] == GUARD).all() and (mp[-64:] == GUARD).all(), tag
+                    got = mp[64:-64].reshape(batch, n)
+                    for b, (name, _, _, _) in enumerate(pats):
+                        assert np.array_equal(got[b], want_flags[b]), \
+                            (tag, b, name, np.flatnonzero(got[b]).tolist()[:8], np.flatnonzero(want_flags[b]).tolist()[:8])
+                else:
+                    assert (mp == GUARD).all(), tag
+                if with_status:
+                    stat = _host(st_d)
+                    assert [tuple(int(x) for x in r) for r in stat] == status, tag
+                    errs = npa.payload_errors(p, stat)
+                    for b, (code, have) in enumerate(status):
+                        assert errs[b] == (npa.NeedMoreShards(have, k, n) if code else None), (tag, b)
+                else:
+                    assert bool((st_d == -1).all()), tag
+                assert np.array_equal(_host(buf), before), tag  # d_shards is only read
+
+
+@pytest.mark.parametrize("nw,kw,sl", DIRECT)
+def test_verify_direct(gpu, oracle, nw, kw, sl):
+    _run_shape(gpu, oracle, nw, kw, sl)
+
+
+@pytest.mark.parametrize("nw,kw,sl", [(1024, 342, 2 * 257), (512, 64, 2 * 259)])
+def test_verify_direct_column_tail(gpu, oracle, nw, kw, sl):
+    """A second tile of 1 and of 3 columns: the per-column path of the compare,
+    where a lane holds fewer than its four columns (300 columns leave whole
+    lanes only).  With offset 2 the rows are at 2-mod-4 addresses."""
+    _run_shape(gpu, oracle, nw, kw, sl)
+
+
+@pytest.mark.parametrize("nw,kw,sl", FALLBACK)
+def test_verify_fallback(gpu, oracle, nw, kw, sl):
+    _run_shape(gpu, oracle, nw, kw, sl)
+
+
+@pytest.mark.parametrize("nw,kw", [(1024, 342), (60, 20)])
+def test_verify_host_single(gpu, oracle, nw, kw):
+    """ReedSolomon.verify / mismatched_shards on odd-length shards (zero padded
+    like WrappedShard and compared over the padded row), and NeedMoreShards
+    raised with the reference's fields."""
+    p = npa.CodeParams.derive_parameters(nw, kw)
+    n, k, wn = p.n(), p.k(), p.wanted_n
+    rng = np.random.default_rng(nw + kw)
+    odd = SL - 1
+
+    def mismatching(received):  # the oracle's answer over the zero-padded rows
+        padded = [None if s is None else s + b"\x00" * (len(s) & 1) for s in received] + [None] * (n - wn)
+        st, pay = oracle.reconstruct(padded, n, k)
+        assert st == 0
+        st, enc = oracle.encode(pay, n, k, wn)
+        assert st == 0
+        return [i for i in range(wn) if padded[i] is not None and padded[i] != enc[i]]
+
+    st, shards = oracle.encode(rng.integers(0, 256, (SL // 2) * 2 * k - 3, dtype=np.uint8).tobytes(), n, k, wn)
+    assert st == 0 and len(shards[0]) == SL
+    pres = np.ones(wn, bool)
+    pres[rng.choice(wn, min((n - k) // 2, wn - k - 1), replace=False)] = False
+    recv = [shards[v] if pres[v] else None for v in range(wn)]
+    rs = p.make_encoder(gpu)
+    # a codeword, then one bit of its last byte (in the partial tile) altered
+    assert rs.verify(recv) is True and rs.mismatched_shards(recv) == []
+    bad = list(recv)
+    v = int(np.flatnonzero(pres[k:])[0]) + k
+    row = bytearray(bad[v])
+    row[SL - 1] ^= 0x10
+    bad[v] = bytes(row)
+    want = mismatching(bad)
+    assert want
+    assert rs.verify(bad) is False and rs.mismatched_shards(bad) == want
+    if kw == npa.recoverablity_subset_size(nw):
+        assert npa.verify(recv, nw, ctx=gpu) is True and npa.verify(bad, nw, ctx=gpu) is False
+    # odd lengths: random bytes with more than k shards, and with exactly k (always consistent)
+    rnd = [rng.integers(0, 256, odd, dtype=np.uint8).tobytes() if pres[i] else None for i in range(wn)]
+    want = mismatching(rnd)
+    assert want and all(i >= k for i in want)
+    assert rs.verify(rnd) is False and rs.mismatched_shards(rnd) == want
+    only_k = list(rnd)
+    for i in np.flatnonzero(pres)[k:]:
+        only_k[i] = None
+    assert mismatching(only_k) == []
+    assert rs.verify(only_k) is True and rs.mismatched_shards(only_k) == []
+    short = list(recv)
+    for i in np.flatnonzero(pres)[k - 1:]:
+        short[i] = None
+    for call in (rs.verify, rs.mismatched_shards):
+        with pytest.raises(npa.NeedMoreShards) as ei:
+            call(short)
+        assert ei.value == npa.NeedMoreShards(k - 1, k, n)
