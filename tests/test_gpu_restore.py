@@ -110,13 +110,19 @@ def _expected_rows(oracle, rows, pres, n, k, wn, sl):
     return {v: enc[v] for v in absent}
 
 
-def _run_shape(gpu, oracle, nw, kw, sl, offset=0, slack=64):
+def expected_rows(oracle, p, sl, pats):
+    """_expected_rows of every payload of `pats` [(name, rows n x sl, present n)]."""
+    return [_expected_rows(oracle, rows, pr, p.n(), p.k(), p.wanted_n, sl) for _, rows, pr in pats]
+
+
+def run_restore(gpu, oracle, p, sl, pats, offset=0, slack=64, expected=None):
+    """One batch of `pats` [(name, rows n x sl, present n)] under `p` (d_shards
+    `offset` bytes into its allocation, batch_stride = n * sl + slack), with and
+    without d_status: every byte of the buffer against the oracle's
+    (`expected`: expected_rows(pats) when the caller shares it between runs)."""
     import torch
 
-    p = npa.CodeParams.derive_parameters(nw, kw)
     n, k, wn = p.n(), p.k(), p.wanted_n
-    rng = np.random.default_rng(1000 * nw + kw + sl + offset)
-    pats = _patterns(oracle, rng, n, k, wn, sl, (nw, kw) in LARGE)
     batch, stride = len(pats), n * sl + slack
     before = np.full(offset + batch * stride + 64, FILL, np.uint8)
     pres = np.stack([pr for _, _, pr in pats])
@@ -125,8 +131,10 @@ def _run_shape(gpu, oracle, nw, kw, sl, offset=0, slack=64):
         view[pr != 0] = rows[pr != 0]
     want = before.copy()  # every byte but the restored rows stays as it was
     status = []
+    if expected is None:
+        expected = expected_rows(oracle, p, sl, pats)
     for b, (name, rows, pr) in enumerate(pats):
-        exp = _expected_rows(oracle, rows, pr, n, k, wn, sl)
+        exp = expected[b]
         status.append((npa.NeedMoreShards.code if exp is None else 0, int(pr.sum())))
         view = want[offset + b * stride: offset + b * stride + n * sl].reshape(n, sl)
         for v, data in (exp or {}).items():
@@ -139,13 +147,16 @@ def _run_shape(gpu, oracle, nw, kw, sl, offset=0, slack=64):
         npa.restore_shards_batch_dev(p, buf.data_ptr() + offset, sl, stride, dpres.data_ptr(), batch, ctx=gpu, stream=s,
                                      d_status=st_d.data_ptr() if with_status else 0)
         got = _host(buf)
+        wrong = []  # every payload that differs, the first in detail
         for b, (name, _, pr) in enumerate(pats):
             lo, hi = offset + b * stride, offset + (b + 1) * stride
             if not np.array_equal(got[lo:hi], want[lo:hi]):
                 bad = np.flatnonzero(got[lo:hi] != want[lo:hi])
                 rows_bad = sorted(set((bad // sl).tolist()))[:8]
-                raise AssertionError(f"payload {b} ({name}), status buffer {with_status}: {bad.size} bytes differ, "
-                                     f"rows {rows_bad} (absent: {[v for v in rows_bad if v < n and not pr[v]]})")
+                wrong.append(f"payload {b} ({name}), status buffer {with_status}: {bad.size} bytes differ, "
+                             f"rows {rows_bad} (absent: {[v for v in rows_bad if v < n and not pr[v]]})")
+        if wrong:
+            raise AssertionError(wrong[0] + f"; {len(wrong)} payloads differ: " + ", ".join(w.split(",")[0] for w in wrong))
         assert np.array_equal(got[:offset], want[:offset]) and np.array_equal(got[-64:], want[-64:])
         if with_status:
             stat = _host(st_d)
@@ -153,6 +164,13 @@ def _run_shape(gpu, oracle, nw, kw, sl, offset=0, slack=64):
             errs = npa.payload_errors(p, stat)
             for b, (code, have) in enumerate(status):
                 assert errs[b] == (npa.NeedMoreShards(have, k, n) if code else None), b
+
+
+def _run_shape(gpu, oracle, nw, kw, sl, offset=0, slack=64):
+    p = npa.CodeParams.derive_parameters(nw, kw)
+    rng = np.random.default_rng(1000 * nw + kw + sl + offset)
+    pats = _patterns(oracle, rng, p.n(), p.k(), p.wanted_n, sl, (nw, kw) in LARGE)
+    run_restore(gpu, oracle, p, sl, pats, offset, slack)
 
 
 @pytest.mark.parametrize("nw,kw,sl", DIRECT)

@@ -1,10 +1,11 @@
-"""np_verify_shards_batch_dev in the checked build (lib/libnovelpoly_hip_chk.so,
--DNP_BOUNDS_CHECK=1; tests/test_gpu_bounds.py): the verify kernels arm the
-extents of the shard rows they read, the present flags, the statuses, the plan,
-the flag map and the counts, and conftest.py's `_bounds_checked` fixture asserts
-after every test of the child that no access fell outside.  The child runs
-tests/test_gpu_verify.py and the verify tests of the segment sweep, the wide
-codes and the fuzz (tests/test_gpu_masked_sweep.py, tests/test_gpu_fuzz_masked.py)."""
+"""np_restore_shards_batch_dev in the checked build (lib/libnovelpoly_hip_chk.so,
+-DNP_BOUNDS_CHECK=1; tests/test_gpu_bounds.py): k_restore_plan, the row-masked
+encode and k_copy_absent_rows arm the extents of the present flags, the
+statuses, the plan, the decoded payloads and the shard rows, and conftest.py's
+`_bounds_checked` fixture asserts after every test of the child that no access
+fell outside.  The child runs tests/test_gpu_restore.py (but its 1 GiB slices
+case) and the restore tests of the segment sweep, the wide codes and the fuzz
+(tests/test_gpu_masked_sweep.py, tests/test_gpu_fuzz_masked.py)."""
 import os
 import subprocess
 import sys
@@ -23,10 +24,10 @@ def _child_env():
 
 
 @pytest.mark.timeout(600)
-def test_verify_kernels_in_bounds():
+def test_restore_kernels_in_bounds():
     assert os.path.exists(CHK_LIB), "run `make -C reed-solomon-novelpoly_amd chk` (__graft_entry__.build does)"
-    r = subprocess.run([sys.executable, "-u", "-m", "pytest", "tests/test_gpu_verify.py", "tests/test_gpu_masked_sweep.py",
-                        "tests/test_gpu_fuzz_masked.py", "-k", "verify", "-m", "gpu", "-x", "-q",
+    r = subprocess.run([sys.executable, "-u", "-m", "pytest", "tests/test_gpu_restore.py", "tests/test_gpu_masked_sweep.py",
+                        "tests/test_gpu_fuzz_masked.py", "-k", "restore and not slices", "-m", "gpu", "-x", "-q",
                         "-p", "no:cacheprovider", "--timeout", "120", "--timeout-method", "thread"],
                        cwd=ROOT, env=_child_env(), capture_output=True, text=True, timeout=580)
     tail = "\n".join((r.stdout + r.stderr).splitlines()[-30:])

@@ -147,12 +147,36 @@ def _expected_flags(oracle, rows, pres, n, k, wn, sl):
         return None
     assert len(pay) == (sl // 2) * 2 * k
     st, enc = oracle.encode(pay, n, k, wn)
-    assert st == 0 and len(enc[0]) == sl
+    assert st == 0 and len(enc) == wn and all(len(e) == sl for e in enc[:1])
     flags = np.zeros(n, np.uint8)
     for v in range(wn):
         if pres[v] and enc[v] != recv[v]:
             flags[v] = 1
     return flags
+
+
+def expected_case(oracle, p, sl, pats):
+    """The oracle's answer for the batch `pats` [(name, rows n x sl, present n,
+    exact)] under `p`: (flags batch x n, counts, [(status, have)]), read only.
+    `exact` is the list of mismatching rows where the pattern fixes it, else None."""
+    n, k, wn = p.n(), p.k(), p.wanted_n
+    flags = np.zeros((len(pats), n), np.uint8)
+    counts, status = [], []
+    for b, (name, rows, pr, exact) in enumerate(pats):
+        exp = _expected_flags(oracle, rows, pr, n, k, wn, sl)
+        if exp is None:
+            assert exact is None, name
+            counts.append(UNDECODABLE)
+            status.append((npa.NeedMoreShards.code, int(pr.sum())))
+            continue
+        if exact is not None:  # the patterns whose answer the semantics fix
+            assert np.flatnonzero(exp).tolist() == exact, (name, np.flatnonzero(exp).tolist(), exact)
+        assert not exp[:k].any(), name  # systematic rows never mismatch
+        flags[b] = exp
+        counts.append(int(exp.sum()))
+        status.append((0, int(pr.sum())))
+    flags.setflags(write=False)
+    return flags, np.asarray(counts, np.uint32), status
 
 
 @functools.lru_cache(maxsize=None)
@@ -162,77 +186,79 @@ def _shape_case(oracle, nw, kw, sl):
     n, k, wn = p.n(), p.k(), p.wanted_n
     rng = np.random.default_rng(1000 * nw + kw + sl)
     pats = _patterns(oracle, rng, n, k, wn, sl, (nw, kw) in LARGE)
-    flags = np.zeros((len(pats), n), np.uint8)
-    counts, status = [], []
-    for b, (name, rows, pr, exact) in enumerate(pats):
-        exp = _expected_flags(oracle, rows, pr, n, k, wn, sl)
-        if exp is None:
-            assert name == "k-1"
-            counts.append(UNDECODABLE)
-            status.append((npa.NeedMoreShards.code, int(pr.sum())))
-            continue
-        assert name != "k-1"
-        if exact is not None:  # the patterns whose answer the semantics fix
-            assert np.flatnonzero(exp).tolist() == exact, (name, np.flatnonzero(exp).tolist(), exact)
-        elif name != "random":
-            assert exp.any(), name  # an altered symbol with > k rows present shows
-        assert not exp[:k].any(), name  # systematic rows never mismatch
-        flags[b] = exp
-        counts.append(int(exp.sum()))
-        status.append((0, int(pr.sum())))
-    for a in (flags,):
-        a.setflags(write=False)
-    return p, pats, flags, np.asarray(counts, np.uint32), status
+    flags, counts, status = expected_case(oracle, p, sl, pats)
+    for b, (name, _, _, exact) in enumerate(pats):
+        assert (counts[b] == UNDECODABLE) == (name == "k-1"), name
+        if name != "k-1" and exact is None and name != "random":
+            assert flags[b].any(), name  # an altered symbol with > k rows present shows
+    return p, pats, flags, counts, status
 
 
-def _run_shape(gpu, oracle, nw, kw, sl):
+# (offset of d_shards in its allocation, batch_stride - n * shard_len, d_status given, d_mismatch given);
+# offset 2, stride n * sl + 2: rows at any even address
+ALL_VARIANTS = tuple((offset, slack, st, mp) for offset, slack in ((0, 64), (2, 2)) for st in (True, False)
+                     for mp in (True, False))
+SWEEP_VARIANTS = ((0, 64, True, True), (2, 2, False, False))
+
+
+def run_verify(gpu, p, sl, pats, expected, variants=ALL_VARIANTS, label=""):
+    """One batch of `pats` under `p` against `expected` (expected_case), once
+    per variant: counts, map, statuses, the guards around them, and d_shards
+    unchanged."""
     import torch
 
-    p, pats, want_flags, want_counts, status = _shape_case(oracle, nw, kw, sl)
+    want_flags, want_counts, status = expected
     n, k = p.n(), p.k()
     batch = len(pats)
     pres = np.stack([pr for _, _, pr, _ in pats])
     dpres = _dev(pres)
     s = torch.cuda.current_stream().cuda_stream
-    for offset, slack in ((0, 64), (2, 2)):  # offset 2, stride n * sl + 2: rows at any even address
+    staged = (None, None, None)  # one staging of the batch per (offset, slack)
+    for offset, slack, with_status, with_map in variants:
         stride = n * sl + slack
-        before = np.full(offset + batch * stride + 64, FILL, np.uint8)
-        for b, (name, rows, pr, _) in enumerate(pats):
-            view = before[offset + b * stride: offset + b * stride + n * sl].reshape(n, sl)
-            view[pr != 0] = rows[pr != 0]
-        buf = _dev(before)
-        for with_status in (True, False):
-            for with_map in (True, False):
-                tag = f"offset {offset}, status {with_status}, map {with_map}"
-                st_d = torch.full((batch, 2), -1, dtype=torch.int32, device="cuda")
-                cnt_d = torch.full((64 + 4 * batch + 64,), GUARD, dtype=torch.uint8, device="cuda")
-                map_d = torch.full((64 + batch * n + 64,), GUARD, dtype=torch.uint8, device="cuda")
-                npa.verify_shards_batch_dev(p, buf.data_ptr() + offset, sl, stride, dpres.data_ptr(), batch,
-                                            cnt_d.data_ptr() + 64, ctx=gpu, stream=s,
-                                            d_mismatch=map_d.data_ptr() + 64 if with_map else 0,
-                                            d_status=st_d.data_ptr() if with_status else 0)
-                cnt, mp = _host(cnt_d), _host(map_d)
-                assert (cnt[:64] == GUARD).all() and (cnt[-64:] == GUARD).all(), tag
-                got_counts = cnt[64:-64].copy().view(np.uint32)
-                print(f"{nw},{kw} {tag}: counts {got_counts.tolist()} want {want_counts.tolist()}")
-                assert got_counts.tolist() == want_counts.tolist(), tag
-                if with_map:
-                    assert (mp[:64] == GUARD).all() and (mp[-64:] == GUARD).all(), tag
-                    got = mp[64:-64].reshape(batch, n)
-                    for b, (name, _, _, _) in enumerate(pats):
-                        assert np.array_equal(got[b], want_flags[b]), \
-                            (tag, b, name, np.flatnonzero(got[b]).tolist()[:8], np.flatnonzero(want_flags[b]).tolist()[:8])
-                else:
-                    assert (mp == GUARD).all(), tag
-                if with_status:
-                    stat = _host(st_d)
-                    assert [tuple(int(x) for x in r) for r in stat] == status, tag
-                    errs = npa.payload_errors(p, stat)
-                    for b, (code, have) in enumerate(status):
-                        assert errs[b] == (npa.NeedMoreShards(have, k, n) if code else None), (tag, b)
-                else:
-                    assert bool((st_d == -1).all()), tag
-                assert np.array_equal(_host(buf), before), tag  # d_shards is only read
+        if staged[0] != (offset, slack):
+            before = np.full(offset + batch * stride + 64, FILL, np.uint8)
+            for b, (name, rows, pr, _) in enumerate(pats):
+                view = before[offset + b * stride: offset + b * stride + n * sl].reshape(n, sl)
+                view[pr != 0] = rows[pr != 0]
+            staged = ((offset, slack), before, _dev(before))
+        _, before, buf = staged
+        tag = f"offset {offset}, status {with_status}, map {with_map}"
+        st_d = torch.full((batch, 2), -1, dtype=torch.int32, device="cuda")
+        cnt_d = torch.full((64 + 4 * batch + 64,), GUARD, dtype=torch.uint8, device="cuda")
+        map_d = torch.full((64 + batch * n + 64,), GUARD, dtype=torch.uint8, device="cuda")
+        npa.verify_shards_batch_dev(p, buf.data_ptr() + offset, sl, stride, dpres.data_ptr(), batch,
+                                    cnt_d.data_ptr() + 64, ctx=gpu, stream=s,
+                                    d_mismatch=map_d.data_ptr() + 64 if with_map else 0,
+                                    d_status=st_d.data_ptr() if with_status else 0)
+        cnt, mp = _host(cnt_d), _host(map_d)
+        assert (cnt[:64] == GUARD).all() and (cnt[-64:] == GUARD).all(), tag
+        got_counts = cnt[64:-64].copy().view(np.uint32)
+        print(f"{label} {tag}: counts {got_counts.tolist()} want {want_counts.tolist()}")
+        wrong = [(int(b), pats[b][0]) for b in np.flatnonzero(got_counts != want_counts)]
+        assert got_counts.tolist() == want_counts.tolist(), (tag, "payloads whose count differs", wrong)
+        if with_map:
+            assert (mp[:64] == GUARD).all() and (mp[-64:] == GUARD).all(), tag
+            got = mp[64:-64].reshape(batch, n)
+            for b, (name, _, _, _) in enumerate(pats):
+                assert np.array_equal(got[b], want_flags[b]), \
+                    (tag, b, name, np.flatnonzero(got[b]).tolist()[:8], np.flatnonzero(want_flags[b]).tolist()[:8])
+        else:
+            assert (mp == GUARD).all(), tag
+        if with_status:
+            stat = _host(st_d)
+            assert [tuple(int(x) for x in r) for r in stat] == status, tag
+            errs = npa.payload_errors(p, stat)
+            for b, (code, have) in enumerate(status):
+                assert errs[b] == (npa.NeedMoreShards(have, k, n) if code else None), (tag, b)
+        else:
+            assert bool((st_d == -1).all()), tag
+        assert np.array_equal(_host(buf), before), tag  # d_shards is only read
+
+
+def _run_shape(gpu, oracle, nw, kw, sl):
+    p, pats, flags, counts, status = _shape_case(oracle, nw, kw, sl)
+    run_verify(gpu, p, sl, pats, (flags, counts, status), label=f"{nw},{kw}")
 
 
 @pytest.mark.parametrize("nw,kw,sl", DIRECT)
