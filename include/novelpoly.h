@@ -269,6 +269,63 @@ int np_restore_shards_batch_dev(np_ctx* ctx, const np_code_params* params, uint8
 int np_verify_shards_batch_dev(np_ctx* ctx, const np_code_params* params, const uint8_t* d_shards, size_t shard_len,
                                size_t batch_stride, const uint8_t* d_present, size_t batch, uint32_t* d_bad_rows,
                                uint8_t* d_mismatch, np_payload_status* d_status, void* stream);
+/* ---- ragged device batches: one call for payloads of different lengths -----
+ * One entry per payload (item).  The same array serves an encode and then the
+ * reconstruct of its shards.  `items` is HOST memory, read before the call
+ * returns and never referenced afterwards. */
+typedef struct np_ragged_item {
+  uint64_t payload_off; /* encode: payload at d_payloads + payload_off; reconstruct: output at d_out + payload_off */
+  uint64_t payload_len; /* encode: bytes, > 0.  reconstruct: ignored */
+  uint64_t shards_off;  /* row v of this item at d_shards + shards_off + v * shard_len */
+  uint64_t shard_len;   /* bytes per row, even, > 0; encode: must equal np_shard_len(params, payload_len) */
+} np_ragged_item;
+
+/* Item b is np_encode_batch_dev with batch = 1 on that payload
+ * (ReedSolomon::encode, mod.rs:117-157); no byte outside rows < wanted_n of an
+ * item is written.  Validation, all on the host before any launch:
+ * payload_len == 0 -> NP_ERR_PAYLOAD_SIZE_IS_ZERO; an odd or zero shard_len ->
+ * NP_ERR_EMPTY_SHARD; NP_ERR_INVALID_ARGUMENT for a shard_len that does not
+ * match payload_len, an odd shards_off, or an extent (payload_off +
+ * payload_len, shards_off + wanted_n * shard_len) past payloads_size /
+ * shards_size.  payload_off may be any byte offset; overlap between items is
+ * the caller's business.  batch == 0 is NP_OK and launches nothing.
+ * Asynchronous on `stream`; the stream is not synchronised.
+ * k in {64, 128, 256} (every n >= 2k): one launch, one workgroup per item and
+ * 256-column tile (np_ragged_plan).  Every other shape: maximal runs of
+ * consecutive items with equal lengths and constant spacing go as one
+ * np_encode_batch_dev-style launch, anything else one item per launch --
+ * correct, and slow for many distinct lengths. */
+int np_encode_ragged_dev(np_ctx* ctx, const np_code_params* params, const uint8_t* d_payloads, size_t payloads_size,
+                         uint8_t* d_shards, size_t shards_size, const np_ragged_item* items, size_t batch,
+                         void* stream);
+/* Item b is np_reconstruct_batch_dev3 with d_locators = NULL and batch = 1:
+ * bit-exact with the reference for any received bytes, the copy mode, the
+ * NeedMoreShards handling (output left untouched) and d_status (device, batch
+ * entries, may be NULL) included.  d_present: device, batch rows of n bytes.
+ * Writes (shard_len / 2) * 2k bytes at d_out + payload_off and nothing else;
+ * reads no absent row.  payload_len is ignored; the extents checked are
+ * shards_off + n * shard_len against shards_size and payload_off +
+ * (shard_len / 2) * 2k against out_size, the rest as np_encode_ragged_dev.
+ * k in {64, 128, 256} with n / k in {2, 4, 8}: one launch (two for n >= 4k, as
+ * the uniform call); every other shape in runs as np_encode_ragged_dev. */
+int np_reconstruct_ragged_dev(np_ctx* ctx, const np_code_params* params, const uint8_t* d_shards, size_t shards_size,
+                              const uint8_t* d_present, uint8_t* d_out, size_t out_size,
+                              const np_ragged_item* items, size_t batch, np_payload_status* d_status, void* stream);
+/* Pure host code, no device needed: validates `items` exactly as the two calls
+ * above do (reconstruct != 0: as np_reconstruct_ragged_dev, payloads_size being
+ * its out_size) and returns the launch plan of the direct path: *nblocks
+ * workgroups, workgroup i working on tile block_tile[i] (256 columns) of item
+ * block_item[i].  Every (item, tile) occurs exactly once; all workgroups of an
+ * item share i % 8 (one XCD's L2 serves the item's records and flags); items
+ * are dealt longest first onto the residue with the fewest tiles so far;
+ * residues that run out are padded with no-op workgroups, block_item[i] ==
+ * UINT32_MAX.  block_item / block_tile may be NULL (count only); cap = their
+ * capacity in entries, NP_ERR_INVALID_ARGUMENT (with *nblocks set) when it is
+ * too small. */
+int np_ragged_plan(const np_code_params* params, const np_ragged_item* items, size_t batch, int reconstruct,
+                   size_t payloads_size, size_t shards_size, uint32_t* block_item, uint32_t* block_tile, size_t cap,
+                   size_t* nblocks);
+
 /* mod.rs:247-285 ReedSolomon::reconstruct_from_systematic for `batch` payloads
  * whose first k shards are all present: d_shards as for np_encode_batch_dev
  * (batch_stride >= k*shard_len, only rows 0..k-1 are read), d_out as for

@@ -365,6 +365,93 @@ impl ReedSolomon {
 		})?;
 		Ok(out)
 	}
+
+	/// The items of a ragged batch of payloads of `lens` bytes, packed one
+	/// after the other: payloads back to back, each item's `wanted_n` (encode)
+	/// or `n` (`rows`) shard rows after the previous item's.  Returns the items
+	/// and the payload and shard buffer sizes they need.
+	pub fn ragged_items(&self, lens: &[usize], rows: usize) -> (Vec<sys::np_ragged_item>, usize, usize) {
+		let (mut poff, mut soff) = (0usize, 0usize);
+		let items = lens
+			.iter()
+			.map(|&len| {
+				let sl = self.shard_len(len);
+				let it = sys::np_ragged_item {
+					payload_off: poff as u64,
+					payload_len: len as u64,
+					shards_off: soff as u64,
+					shard_len: sl as u64,
+				};
+				poff += sl / 2 * 2 * self.params.raw.k; // room for the reconstruct's padded output
+				soff += rows * sl;
+				it
+			})
+			.collect();
+		(items, poff, soff)
+	}
+
+	/// np_encode_ragged_dev: one call for payloads of different lengths in
+	/// device memory.  Asynchronous on `stream`; `items` is read before the
+	/// call returns.
+	///
+	/// # Safety
+	/// `d_payloads` / `d_shards` must be device allocations of at least
+	/// `payloads_size` / `shards_size` bytes on the context's device, valid
+	/// until the stream has run the call.
+	pub unsafe fn encode_ragged_dev(
+		&self,
+		d_payloads: *const u8,
+		payloads_size: usize,
+		d_shards: *mut u8,
+		shards_size: usize,
+		items: &[sys::np_ragged_item],
+		stream: *mut std::ffi::c_void,
+	) -> Result<()> {
+		check(sys::np_encode_ragged_dev(
+			self.ctx.raw,
+			&self.params.raw,
+			d_payloads,
+			payloads_size,
+			d_shards,
+			shards_size,
+			items.as_ptr(),
+			items.len(),
+			stream,
+		))
+	}
+
+	/// np_reconstruct_ragged_dev: the reconstruct of every item's shards
+	/// (`d_present`: `items.len() * n` device flags), each into
+	/// `d_out + payload_off`; `d_status` (device, one entry per item) may be
+	/// null.  Asynchronous on `stream`.
+	///
+	/// # Safety
+	/// As `encode_ragged_dev`, for `d_shards`, `d_present`, `d_out` and `d_status`.
+	pub unsafe fn reconstruct_ragged_dev(
+		&self,
+		d_shards: *const u8,
+		shards_size: usize,
+		d_present: *const u8,
+		d_out: *mut u8,
+		out_size: usize,
+		items: &[sys::np_ragged_item],
+		d_status: *mut sys::np_payload_status,
+		stream: *mut std::ffi::c_void,
+	) -> Result<()> {
+		check(sys::np_reconstruct_ragged_dev(
+			self.ctx.raw,
+			&self.params.raw,
+			d_shards,
+			shards_size,
+			d_present,
+			d_out,
+			out_size,
+			items.as_ptr(),
+			items.len(),
+			d_status,
+			stream,
+		))
+	}
 }
 
 /// encode.rs:6-11: derives (n, k) from the validator count like the crate.

@@ -23,6 +23,17 @@ pub struct np_payload_status {
 	pub have: u32,
 }
 
+/// `np_ragged_item`: one payload of a ragged device batch (offsets into the
+/// caller's buffers, lengths in bytes).
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default, PartialEq, Eq)]
+pub struct np_ragged_item {
+	pub payload_off: u64,
+	pub payload_len: u64,
+	pub shards_off: u64,
+	pub shard_len: u64,
+}
+
 /// Opaque `np_ctx` (one per GPU).
 #[repr(C)]
 pub struct np_ctx {
@@ -139,6 +150,42 @@ extern "C" {
 		d_mismatch: *mut u8,
 		d_status: *mut np_payload_status,
 		stream: *mut c_void,
+	) -> c_int;
+	pub fn np_encode_ragged_dev(
+		ctx: *mut np_ctx,
+		params: *const np_code_params,
+		d_payloads: *const u8,
+		payloads_size: usize,
+		d_shards: *mut u8,
+		shards_size: usize,
+		items: *const np_ragged_item,
+		batch: usize,
+		stream: *mut c_void,
+	) -> c_int;
+	pub fn np_reconstruct_ragged_dev(
+		ctx: *mut np_ctx,
+		params: *const np_code_params,
+		d_shards: *const u8,
+		shards_size: usize,
+		d_present: *const u8,
+		d_out: *mut u8,
+		out_size: usize,
+		items: *const np_ragged_item,
+		batch: usize,
+		d_status: *mut np_payload_status,
+		stream: *mut c_void,
+	) -> c_int;
+	pub fn np_ragged_plan(
+		params: *const np_code_params,
+		items: *const np_ragged_item,
+		batch: usize,
+		reconstruct: c_int,
+		payloads_size: usize,
+		shards_size: usize,
+		block_item: *mut u32,
+		block_tile: *mut u32,
+		cap: usize,
+		nblocks: *mut usize,
 	) -> c_int;
 	pub fn np_rs_reconstruct_from_systematic(
 		ctx: *mut np_ctx,

@@ -49,7 +49,9 @@ __device__ __forceinline__ uint16_t be_sym(const uint8_t* p, size_t off, size_t 
 // checked against the extents of an earlier launch (round 6: k_big_records
 // was, and flagged its own present flags against another launch's batch).
 enum BoundsKind : uint32_t {
-  kBkShards, kBkPresent, kBkLocators, kBkRecords, kBkOut, kBkStatus, kBkZeros, kBkPayloads, kBkCount
+  kBkShards, kBkPresent, kBkLocators, kBkRecords, kBkOut, kBkStatus, kBkZeros, kBkPayloads,
+  kBkItems, kBkBlocks,  // the ragged kernels' item records and block table
+  kBkCount
 };
 struct BoundsSet {
   uint64_t lo[kBkCount], hi[kBkCount];

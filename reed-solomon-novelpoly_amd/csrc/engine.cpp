@@ -156,6 +156,17 @@ struct np_ctx {
   size_t restore_cap = size_t(256) << 20;  // big_cap / 8: set at creation
   hipEvent_t restore_done = nullptr;
   bool restore_used = false;
+  // np_encode_ragged_dev / np_reconstruct_ragged_dev: the device copy of a
+  // call's plan (item records, block table), ordered across streams through
+  // ragged_done the same way.  It is uploaded from a ring of pinned staging
+  // buffers; each is reused only after the event of its last upload.
+  DevBuf d_ragged;
+  hipEvent_t ragged_done = nullptr;
+  bool ragged_used = false;
+  static constexpr int kRaggedStage = 4;
+  HostBuf h_ragged[kRaggedStage];
+  hipEvent_t ragged_ev[kRaggedStage] = {};
+  unsigned ragged_next = 0;
   // Host-memory batch pipeline (np_*_batch_host): per slot a stream and
   // device buffers for one sub-batch; created on first use.
   static constexpr int kPipe = 6;  // at most; pipe_slots() are used
@@ -738,6 +749,13 @@ void np_ctx_destroy(np_ctx* c) {
   if (c->big_done) (void)hipEventDestroy(c->big_done);
   c->d_restore.release();
   if (c->restore_done) (void)hipEventDestroy(c->restore_done);
+  c->d_ragged.release();
+  if (c->ragged_done) (void)hipEventDestroy(c->ragged_done);
+  for (int i = 0; i < np_ctx::kRaggedStage; ++i) {
+    if (c->ragged_ev[i]) (void)hipEventSynchronize(c->ragged_ev[i]);
+    c->h_ragged[i].release();
+    if (c->ragged_ev[i]) (void)hipEventDestroy(c->ragged_ev[i]);
+  }
   for (int i = 0; i < np_ctx::kPipe; ++i) {
     if (c->pipe_s[i]) (void)hipStreamSynchronize(c->pipe_s[i]);
     c->pipe_in[i].release();
@@ -1872,6 +1890,330 @@ int np_reconstruct_from_systematic_batch_dev(np_ctx* c, const np_code_params* p,
   (void)hipSetDevice(c->device);
   return dev_err(HIP(np::launch_systematic(d_shards, shard_len, bstride, static_cast<uint32_t>(p->k), batch, d_out,
                                        out_stride, pick(c, stream))));
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------- ragged batches ----
+// One call for a batch whose payloads differ in length (np_ragged_item).
+// Direct shapes (k in {64, 128, 256}): the host plans one workgroup per item
+// and 256-column tile (ragged_plan), uploads the item records and the block
+// table through pinned staging into context scratch, and launches the ragged
+// kernels of kernels_fast.hip.  Every other shape: runs of equal items at a
+// constant spacing through the uniform launch_encode / launch_reconstruct.
+namespace {
+
+constexpr size_t kRaggedTile = 256;  // columns per workgroup (kernels_fast.hip kTile)
+
+bool past(uint64_t off, uint64_t len, uint64_t size) { return off > size || len > size - off; }
+
+// The validation of both ragged calls and of np_ragged_plan.
+int ragged_validate(const np_code_params* p, const np_ragged_item* items, size_t batch, bool reconstruct,
+                    size_t data_size, size_t shards_size) {
+  int st = check_params(p);
+  if (st) return st;
+  if (batch && !items) return fail(NP_ERR_INVALID_ARGUMENT);
+  if (batch >= 0xffffffffu) return fail(NP_ERR_INVALID_ARGUMENT, batch);
+  const uint64_t rows = reconstruct ? p->n : p->wanted_n;
+  for (size_t b = 0; b < batch; ++b) {
+    const np_ragged_item& it = items[b];
+    if (!reconstruct && it.payload_len == 0) return fail(NP_ERR_PAYLOAD_SIZE_IS_ZERO, b);
+    if (it.shard_len == 0 || (it.shard_len & 1)) return fail(NP_ERR_EMPTY_SHARD, b);
+    if (!reconstruct && it.shard_len != np_shard_len(p, it.payload_len)) return fail(NP_ERR_INVALID_ARGUMENT, b);
+    if (it.shards_off & 1) return fail(NP_ERR_INVALID_ARGUMENT, b);
+    const uint64_t cols = it.shard_len / 2;
+    if (cols > 0xffffffffu) return fail(NP_ERR_INVALID_ARGUMENT, b);
+    if (rows && it.shard_len > UINT64_MAX / rows) return fail(NP_ERR_INVALID_ARGUMENT, b);
+    if (past(it.shards_off, rows * it.shard_len, shards_size)) return fail(NP_ERR_INVALID_ARGUMENT, b);
+    uint64_t data_len = it.payload_len;
+    if (reconstruct) {
+      if (cols > UINT64_MAX / (2 * p->k)) return fail(NP_ERR_INVALID_ARGUMENT, b);
+      data_len = cols * 2 * p->k;
+    }
+    if (past(it.payload_off, data_len, data_size)) return fail(NP_ERR_INVALID_ARGUMENT, b);
+  }
+  return NP_OK;
+}
+
+// The launch plan of items [b0, b0 + cnt) (item numbers relative to b0): one
+// block per (item, tile).  Items are dealt longest first to the 8 residues of
+// the block index mod 8 (the XCD a workgroup lands on), each onto the residue
+// with the fewest tiles so far; the residues' blocks are interleaved, and a
+// residue that ran out is padded with no-op blocks up to the last real one.
+void ragged_plan(const np_ragged_item* items, size_t b0, size_t cnt, std::vector<uint32_t>* block_item,
+                 std::vector<uint32_t>* block_tile, size_t* nblocks) {
+  auto tiles_of = [&](size_t i) { return (items[b0 + i].shard_len / 2 + kRaggedTile - 1) / kRaggedTile; };
+  std::vector<uint32_t> order(cnt);
+  for (size_t i = 0; i < cnt; ++i) order[i] = static_cast<uint32_t>(i);
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return tiles_of(x) > tiles_of(y); });
+  std::vector<uint32_t> of[8];  // the items of each residue, in dealing order
+  size_t load[8] = {};
+  for (uint32_t i : order) {
+    const size_t r = static_cast<size_t>(std::min_element(load, load + 8) - load);
+    of[r].push_back(i);
+    load[r] += tiles_of(i);
+  }
+  size_t last = 0;  // blocks up to the last real one
+  for (size_t r = 0; r < 8; ++r)
+    if (load[r]) last = std::max(last, 8 * (load[r] - 1) + r + 1);
+  *nblocks = last;
+  if (!block_item || !block_tile) return;
+  block_item->assign(last, np::kRaggedNoItem);
+  block_tile->assign(last, 0);
+  for (size_t r = 0; r < 8; ++r) {
+    size_t j = 0;
+    for (uint32_t i : of[r])
+      for (size_t t = 0, nt = tiles_of(i); t < nt; ++t, ++j) {
+        (*block_item)[8 * j + r] = i;
+        (*block_tile)[8 * j + r] = static_cast<uint32_t>(t);
+      }
+  }
+}
+
+size_t align16(size_t x) { return (x + 15) / 16 * 16; }
+
+// The plan of a direct launch in device memory: the records of `recs`, then
+// the block table.  The bytes go through a pinned staging buffer of the
+// context's ring (no pageable pointer reaches a HIP copy, §4.7), which is
+// reused only after the event recorded behind its upload; the device copy is
+// ordered after every earlier ragged launch of the context on any stream
+// (ragged_done; the caller records it behind the launch).  Caller holds the
+// context lock.
+hipError_t ragged_upload(np_ctx* c, const std::vector<np::RaggedRec>& recs, const std::vector<uint32_t>& block_item,
+                         const std::vector<uint32_t>& block_tile, hipStream_t s, np::RaggedArgs* r) {
+  const size_t o_item = align16(recs.size() * sizeof(np::RaggedRec));
+  const size_t o_tile = o_item + align16(block_item.size() * sizeof(uint32_t));
+  const size_t bytes = o_tile + align16(block_tile.size() * sizeof(uint32_t));
+  hipError_t e = hipSuccess;
+  if (!c->ragged_done) e = HIP(hipEventCreateWithFlags(&c->ragged_done, hipEventDisableTiming));
+  if (e == hipSuccess && c->ragged_used) {
+    if (bytes > c->d_ragged.cap) e = HIP(hipEventSynchronize(c->ragged_done));  // about to free the old buffer
+    if (e == hipSuccess) e = HIP(hipStreamWaitEvent(s, c->ragged_done, 0));
+  }
+  if (e == hipSuccess) {
+    e = HIP(c->d_ragged.ensure(bytes));
+    if (e != hipSuccess) e = hipErrorOutOfMemory;  // NP_ERR_ALLOC
+  }
+  if (e != hipSuccess) return e;
+  const unsigned slot = c->ragged_next++ % np_ctx::kRaggedStage;
+  HostBuf& h = c->h_ragged[slot];
+  if (!c->ragged_ev[slot])
+    e = HIP(hipEventCreateWithFlags(&c->ragged_ev[slot], hipEventDisableTiming));
+  else
+    e = HIP(hipEventSynchronize(c->ragged_ev[slot]));  // its last upload has left the buffer
+  if (e == hipSuccess) {
+    e = HIP(h.ensure(bytes));
+    if (e != hipSuccess) e = hipErrorOutOfMemory;
+  }
+  if (e != hipSuccess) return e;
+  uint8_t* hp = h.as<uint8_t>();
+  std::memcpy(hp, recs.data(), recs.size() * sizeof(np::RaggedRec));
+  std::memcpy(hp + o_item, block_item.data(), block_item.size() * sizeof(uint32_t));
+  std::memcpy(hp + o_tile, block_tile.data(), block_tile.size() * sizeof(uint32_t));
+  uint8_t* dp = c->d_ragged.as<uint8_t>();
+  e = HIP(hipMemcpyAsync(dp, hp, bytes, hipMemcpyHostToDevice, s));
+  if (e == hipSuccess) e = HIP(hipEventRecord(c->ragged_ev[slot], s));
+  r->recs = reinterpret_cast<const np::RaggedRec*>(dp);
+  r->block_item = reinterpret_cast<const uint32_t*>(dp + o_item);
+  r->block_tile = reinterpret_cast<const uint32_t*>(dp + o_tile);
+  r->nitems = static_cast<uint32_t>(recs.size());
+  r->nblocks = static_cast<uint32_t>(block_item.size());
+  return e;
+}
+
+hipError_t ragged_done(np_ctx* c, hipStream_t s, hipError_t e) {
+  if (e != hipSuccess) return e;
+  c->ragged_used = true;
+  return HIP(hipEventRecord(c->ragged_done, s));
+}
+
+// Items [b0, b0 + cnt) as device records: absolute addresses.
+std::vector<np::RaggedRec> ragged_recs(const np_ragged_item* items, size_t b0, size_t cnt, const uint8_t* data,
+                                       const uint8_t* shards) {
+  std::vector<np::RaggedRec> recs(cnt);
+  for (size_t i = 0; i < cnt; ++i) {
+    const np_ragged_item& it = items[b0 + i];
+    recs[i] = np::RaggedRec{reinterpret_cast<uint64_t>(data) + it.payload_off, it.payload_len,
+                            reinterpret_cast<uint64_t>(shards) + it.shards_off, it.shard_len};
+  }
+  return recs;
+}
+
+np::RaggedArgs ragged_args(const np_code_params* p, const uint8_t* data, size_t data_size, const uint8_t* shards,
+                           size_t shards_size) {
+  np::RaggedArgs r{};
+  r.n = static_cast<uint32_t>(p->n);
+  r.k = static_cast<uint32_t>(p->k);
+  r.wanted_n = static_cast<uint32_t>(p->wanted_n);
+  r.data_base = data;
+  r.data_size = data_size;
+  r.shards_base = shards;
+  r.shards_size = shards_size;
+  return r;
+}
+
+// The end of the run of items starting at b0 that one uniform call serves:
+// equal lengths, and offsets that advance by one constant stride each, no
+// smaller than an item's extent (data_len(b) / rows * shard_len).
+template <class F>
+size_t ragged_run(const np_ragged_item* items, size_t b0, size_t batch, bool reconstruct, uint64_t rows, F data_len,
+                  uint64_t* dstride, uint64_t* sstride) {
+  const np_ragged_item& a = items[b0];
+  *dstride = data_len(a);
+  *sstride = rows * a.shard_len;
+  size_t e = b0 + 1;
+  for (; e < batch; ++e) {
+    const np_ragged_item &x = items[e], &prev = items[e - 1];
+    if (x.shard_len != a.shard_len || (!reconstruct && x.payload_len != a.payload_len)) break;
+    if (x.payload_off <= prev.payload_off || x.shards_off <= prev.shards_off) break;
+    const uint64_t dd = x.payload_off - prev.payload_off, ds = x.shards_off - prev.shards_off;
+    if (e == b0 + 1) {
+      if (dd < data_len(a) || ds < rows * a.shard_len) break;
+      *dstride = dd;
+      *sstride = ds;
+    } else if (dd != *dstride || ds != *sstride) {
+      break;
+    }
+  }
+  return e;
+}
+
+hipError_t launch_encode_ragged_all(np_ctx* c, const np_code_params* p, const uint8_t* d_payloads,
+                                    size_t payloads_size, uint8_t* d_shards, size_t shards_size,
+                                    const np_ragged_item* items, size_t batch, hipStream_t s) {
+  const uint32_t n = static_cast<uint32_t>(p->n), k = static_cast<uint32_t>(p->k);
+  if (np::ragged_encode_supported(n, k)) {
+    std::vector<uint32_t> bi, bt;
+    size_t nblocks = 0;
+    ragged_plan(items, 0, batch, &bi, &bt, &nblocks);
+    np::RaggedArgs r = ragged_args(p, d_payloads, payloads_size, d_shards, shards_size);
+    hipError_t e = ragged_upload(c, ragged_recs(items, 0, batch, d_payloads, d_shards), bi, bt, s, &r);
+    if (e == hipSuccess) e = HIP(np::launch_encode_ragged(c->T, r, s));
+    return ragged_done(c, s, e);
+  }
+  for (size_t b0 = 0; b0 < batch;) {
+    uint64_t pstride = 0, bstride = 0;
+    const size_t b1 = ragged_run(items, b0, batch, false, p->wanted_n,
+                                 [](const np_ragged_item& it) { return it.payload_len; }, &pstride, &bstride);
+    const np_ragged_item& it = items[b0];
+    hipError_t e = launch_encode(c, enc_args(p, d_payloads + it.payload_off, it.payload_len, pstride, b1 - b0,
+                                             d_shards + it.shards_off, bstride), s);
+    if (e != hipSuccess) return e;
+    b0 = b1;
+  }
+  return hipSuccess;
+}
+
+hipError_t launch_reconstruct_ragged_all(np_ctx* c, const np_code_params* p, const uint8_t* d_shards,
+                                         size_t shards_size, const uint8_t* d_present, uint8_t* d_out,
+                                         size_t out_size, const np_ragged_item* items, size_t batch,
+                                         uint32_t* d_status, hipStream_t s) {
+  const uint32_t n = static_cast<uint32_t>(p->n), k = static_cast<uint32_t>(p->k);
+  np::ReconstructArgs a{};
+  a.locators = nullptr;  // computed on the device
+  a.n = n;
+  a.k = k;
+  if (np::ragged_reconstruct_supported(n, k)) {
+    // per slice of the batch: the prefix records (and the status) of its items
+    // in the ordered context scratch, as launch_reconstruct's fast path
+    const size_t own_status = d_status ? 0 : kStatusBytes;
+    const size_t stride = np::prefix_stride(n, k);
+    const size_t per = std::max<size_t>(1, c->big_cap / (stride + own_status));
+    for (size_t b0 = 0; b0 < batch; b0 += per) {
+      const size_t cnt = std::min(per, batch - b0);
+      uint8_t* scr = nullptr;
+      size_t bytes = 0;
+      hipError_t e = big_scratch(c, cnt * (stride + own_status), s, &scr, &bytes);
+      a.present = d_present + b0 * p->n;
+      a.batch = cnt;
+      a.status = d_status ? d_status + 2 * b0 : reinterpret_cast<uint32_t*>(scr + cnt * stride);
+      if (e == hipSuccess) e = HIP(np::launch_prefix_locator(c->T, a, scr, s));
+      std::vector<uint32_t> bi, bt;
+      size_t nblocks = 0;
+      ragged_plan(items, b0, cnt, &bi, &bt, &nblocks);
+      np::RaggedArgs r = ragged_args(p, d_out, out_size, d_shards, shards_size);
+      r.present = a.present;
+      r.prefix = scr;
+      r.status = a.status;
+      if (e == hipSuccess) e = ragged_upload(c, ragged_recs(items, b0, cnt, d_out, d_shards), bi, bt, s, &r);
+      if (e == hipSuccess) e = HIP(np::launch_reconstruct_ragged(c->T, r, s));
+      e = big_done(c, s, e);
+      e = ragged_done(c, s, e);
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  }
+  const uint64_t out_len_k = 2 * static_cast<uint64_t>(p->k);
+  for (size_t b0 = 0; b0 < batch;) {
+    uint64_t ostride = 0, bstride = 0;
+    const size_t b1 = ragged_run(items, b0, batch, true, p->n,
+                                 [&](const np_ragged_item& it) { return (it.shard_len / 2) * out_len_k; }, &ostride,
+                                 &bstride);
+    const np_ragged_item& it = items[b0];
+    a.shards = d_shards + it.shards_off;
+    a.shard_len = it.shard_len;
+    a.batch_stride = bstride;
+    a.present = d_present + b0 * p->n;
+    a.batch = b1 - b0;
+    a.out = d_out + it.payload_off;
+    a.out_stride = ostride;
+    a.status = d_status ? d_status + 2 * b0 : nullptr;
+    hipError_t e = launch_reconstruct(c, a, s);
+    if (e != hipSuccess) return e;
+    b0 = b1;
+  }
+  return hipSuccess;
+}
+
+}  // namespace
+
+extern "C" {
+
+int np_ragged_plan(const np_code_params* p, const np_ragged_item* items, size_t batch, int reconstruct,
+                   size_t payloads_size, size_t shards_size, uint32_t* block_item, uint32_t* block_tile, size_t cap,
+                   size_t* nblocks) {
+  if (!nblocks) return fail(NP_ERR_INVALID_ARGUMENT);
+  *nblocks = 0;
+  int st = ragged_validate(p, items, batch, reconstruct != 0, payloads_size, shards_size);
+  if (st) return st;
+  if (!block_item || !block_tile) {
+    ragged_plan(items, 0, batch, nullptr, nullptr, nblocks);
+    return NP_OK;
+  }
+  std::vector<uint32_t> bi, bt;
+  ragged_plan(items, 0, batch, &bi, &bt, nblocks);
+  if (*nblocks > cap) return fail(NP_ERR_INVALID_ARGUMENT, *nblocks, cap);
+  std::copy(bi.begin(), bi.end(), block_item);
+  std::copy(bt.begin(), bt.end(), block_tile);
+  return NP_OK;
+}
+
+int np_encode_ragged_dev(np_ctx* c, const np_code_params* p, const uint8_t* d_payloads, size_t payloads_size,
+                         uint8_t* d_shards, size_t shards_size, const np_ragged_item* items, size_t batch,
+                         void* stream) {
+  if (!c) return fail(NP_ERR_INVALID_ARGUMENT);
+  int st = ragged_validate(p, items, batch, false, payloads_size, shards_size);
+  if (st) return st;
+  if (batch == 0) return NP_OK;
+  if (!d_payloads || !d_shards) return fail(NP_ERR_INVALID_ARGUMENT);
+  std::lock_guard<std::mutex> g(c->mu);  // context scratch
+  (void)hipSetDevice(c->device);
+  return dev_err(launch_encode_ragged_all(c, p, d_payloads, payloads_size, d_shards, shards_size, items, batch,
+                                          pick(c, stream)));
+}
+
+int np_reconstruct_ragged_dev(np_ctx* c, const np_code_params* p, const uint8_t* d_shards, size_t shards_size,
+                              const uint8_t* d_present, uint8_t* d_out, size_t out_size,
+                              const np_ragged_item* items, size_t batch, np_payload_status* d_status, void* stream) {
+  if (!c) return fail(NP_ERR_INVALID_ARGUMENT);
+  int st = ragged_validate(p, items, batch, true, out_size, shards_size);
+  if (st) return st;
+  if (batch == 0) return NP_OK;
+  if (!d_shards || !d_present || !d_out) return fail(NP_ERR_INVALID_ARGUMENT);
+  std::lock_guard<std::mutex> g(c->mu);  // context scratch
+  (void)hipSetDevice(c->device);
+  return dev_err(launch_reconstruct_ragged_all(c, p, d_shards, shards_size, d_present, d_out, out_size, items, batch,
+                                               reinterpret_cast<uint32_t*>(d_status), pick(c, stream)));
 }
 
 // ------------------------------------------------------------ multi-GPU ----

@@ -1791,7 +1791,8 @@ hipError_t launch_reconstruct_fast(const DevTables& T, const ReconstructArgs& a,
 
 namespace {
 hipError_t configure_masked_kernels();  // below, with the masked encode's launchers
-hipError_t configure_verify_kernels();  // at the end of the file, with the verify encode
+hipError_t configure_verify_kernels();  // with the verify encode
+hipError_t configure_ragged_kernels();  // at the end of the file, with the ragged kernels
 }
 
 hipError_t configure_fast_kernels() {
@@ -1821,6 +1822,7 @@ hipError_t configure_fast_kernels() {
   set(reinterpret_cast<const void*>(&k_reconstruct_fast<256, 8, 8>), reconstruct_lds_bytes<256, 8>());
   if (e == hipSuccess) e = configure_masked_kernels();
   if (e == hipSuccess) e = configure_verify_kernels();
+  if (e == hipSuccess) e = configure_ragged_kernels();
   return e;
 }
 
@@ -2147,6 +2149,293 @@ hipError_t launch_encode_verify(const DevTables& T, const EncodeArgs& a, const u
     case 64: return launch_encode_verify_k<64>(T, a, plan, flags, s);
     case 128: return launch_encode_verify_k<128>(T, a, plan, flags, s);
     case 256: return launch_encode_verify_k<256>(T, a, plan, flags, s);
+    default: return hipErrorNotSupported;
+  }
+}
+
+// ---------------------------------------------------------- ragged batches ----
+// np_encode_ragged_dev / np_reconstruct_ragged_dev: the single-tile flows of
+// k_encode_fast and k_reconstruct_fast on a batch whose items differ in length
+// and sit anywhere in the caller's buffers.  The workgroup head reads its
+// (item, tile) from the block table of the host's plan (np_ragged_plan) and the
+// item's addresses and lengths from its RaggedRec with scalar loads; what the
+// uniform kernels derive per launch (the column count, `full`, the streaming
+// stores, the tile load's fast test) is derived per item.  Padding entries of
+// the table (kRaggedNoItem) exit, workgroup-uniformly, before any barrier of
+// the flow.  The present flags, the prefix records and the status stay per
+// item at their fixed strides.
+// The last kernels of this file: every older kernel's assembly stays what it was.
+namespace {
+
+typedef const __attribute__((address_space(4))) uint64_t* crec_t;
+
+struct RaggedHead {
+  uint32_t item, tile;
+  uint64_t data, data_len, shards, shard_len;
+};
+
+// The workgroup's block-table entry and its item's record (wave-uniform).
+__device__ __forceinline__ RaggedHead ragged_head(const RaggedArgs& r) {
+  RaggedHead h{};
+  NP_BNOTE(r.block_item + blockIdx.x, 4, kBkBlocks);
+  NP_BNOTE(r.block_tile + blockIdx.x, 4, kBkBlocks);
+  h.item = ((cpool_t)(r.block_item))[blockIdx.x];
+  if (h.item == kRaggedNoItem) return h;
+  h.tile = ((cpool_t)(r.block_tile))[blockIdx.x];
+  NP_BNOTE(r.recs + h.item, sizeof(RaggedRec), kBkItems);
+  const crec_t rec = (crec_t)(r.recs + h.item);
+  h.data = rec[0], h.data_len = rec[1], h.shards = rec[2], h.shard_len = rec[3];
+  return h;
+}
+
+#if NP_BOUNDS_CHECK
+__device__ __forceinline__ BoundsSet bounds_of_ragged(const RaggedArgs& r, const DevTables& T, bool reconstruct) {
+  BoundsSet b{};
+  auto set = [&](uint32_t k, const void* p, uint64_t bytes) {
+    if (!p || bytes == 0) return;
+    b.lo[k] = reinterpret_cast<uint64_t>(p);
+    b.hi[k] = b.lo[k] + bytes;
+  };
+  set(reconstruct ? kBkOut : kBkPayloads, r.data_base, r.data_size);
+  set(kBkShards, r.shards_base, r.shards_size);
+  set(kBkItems, r.recs, static_cast<uint64_t>(r.nitems) * sizeof(RaggedRec));
+  // both arrays of the block table: the tiles follow the items in one allocation
+  set(kBkBlocks, r.block_item, static_cast<uint64_t>(r.block_tile + r.nblocks - r.block_item) * 4u);
+  if (reconstruct) {
+    set(kBkPresent, r.present, static_cast<uint64_t>(r.nitems) * r.n);
+    set(kBkRecords, r.prefix, static_cast<uint64_t>(r.nitems) * prefix_stride_c(r.n, r.k));
+    set(kBkStatus, r.status, static_cast<uint64_t>(r.nitems) * 8u);
+    set(kBkZeros, T.zeros, kZeroPageBytes);
+  }
+  return b;
+}
+#endif
+
+// One workgroup: 256 chunks of one item (k_encode_fast's flow).
+template <int K>
+__global__ __launch_bounds__(4 * K) __attribute__((amdgpu_waves_per_eu(4))) void k_encode_ragged(DevTables T, RaggedArgs r) {
+  using G = Geo<K>;
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  uint8_t* tile = smem;
+  uint32_t* VP = reinterpret_cast<uint32_t*>(smem + G::kTileBytes);  // 2 staged transforms
+#if NP_BOUNDS_CHECK
+  bounds_arm(bounds_of_ragged(r, T, false));
+#endif
+  const RaggedHead h = ragged_head(r);
+  if (h.item == kRaggedNoItem) return;  // padding of the plan
+  const uint8_t* pay = reinterpret_cast<const uint8_t*>(h.data);
+  const size_t payload_len = h.data_len, shard_len = h.shard_len;
+  uint8_t* const shards = reinterpret_cast<uint8_t*>(h.shards);
+  const uint32_t nchunks = static_cast<uint32_t>(shard_len / 2);  // = ceil(payload_len / 2K), validated by the host
+  const uint32_t ch0 = h.tile * kTile;
+  const uint32_t ncols = min(static_cast<uint32_t>(kTile), nchunks - ch0);
+  uint8_t* out = shards + 2 * static_cast<size_t>(ch0);
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, g = uniform(tid >> 6);
+  const bool full = ncols == kTile && rows_vec_ok(shards, 0, shard_len);
+
+  // ---- tile load: thread tid moves blocks (c0 + 16 i, m0), i = 0..15
+  {
+    const uint32_t c0 = tid / G::Q, m0 = tid % G::Q;
+    const uint32_t base = col_base<K>(c0) ^ (8u * m0);
+    const size_t gbase = static_cast<size_t>(ch0 + c0) * 2 * K + 8u * m0;
+    const bool fast = out_vec_ok(pay, 0) && static_cast<size_t>(ch0 + kTile) * 2 * K <= payload_len;
+    if (fast) {
+      uint2 v[16];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) v[i] = load_once(pay + gbase + static_cast<size_t>(i) * 32 * K);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) *reinterpret_cast<uint2*>(tile + (base ^ col_base_c<K>(16u * i))) = v[i];
+    } else {
+#pragma unroll 1
+      for (uint32_t i = 0; i < 16; ++i) {
+        const size_t g0 = gbase + static_cast<size_t>(i) * 32 * K;
+        uint32_t w[2] = {0, 0};
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (g0 + e < payload_len) w[e >> 2] |= static_cast<uint32_t>(*NP_BCHK(pay + (g0 + e), 1, kBkPayloads)) << (8 * (e & 3));
+        *reinterpret_cast<uint2*>(tile + (base ^ col_base_c<K>(16u * i))) = make_uint2(w[0], w[1]);
+      }
+    }
+  }
+  const uint32_t nshift = r.n / K;
+  const uint32_t wanted_n = r.wanted_n;
+  const bool nt = rows_nt(shards, 0, shard_len);
+  // n <= 4K: the tables of every transform stay staged; otherwise two buffers alternate
+  const bool resident = nshift <= 4;
+  if (resident) {
+    for (uint32_t sh = 0; sh < nshift && sh * K < wanted_n; ++sh)
+      stage_vpools<K, G::kThreads>(T, sh * K, VP + sh * G::kVPWords, true, enc_conv(K, sh));
+  } else {
+    stage_vpools<K, G::kThreads>(T, 0, VP, true);                                   // inverse transform, index 0
+    if (nshift > 1) stage_vpools<K, G::kThreads>(T, K, VP + G::kVPWords, true, enc_conv(K, 1));  // first shift
+  }
+  __syncthreads();
+
+  const uint32_t cqb = col_base<K>(4 * lane) ^ (32u * g);  // blocks 4g..4g+3 of columns 4l..4l+3
+  // ---- cq pass: systematic rows, inverse levels 0..3
+  {
+    uint32_t CL[16], CH[16];
+    cq_read<K>(tile, cqb, CL, CH);
+    store_rows(out, shard_len, 16 * g, wanted_n, CL, CH, lane, ncols, full, nt);
+    tower_convert(T, CL, CH);  // transforms run in tower coordinates
+    cq_levels<K, true, true, 0, false, kEncPrioCq>(T, VP, 0, g, CL, CH);
+    // the quad items overlay payload blocks that other waves read: wait for
+    // every wave's cq_read
+    __syncthreads();
+    cq_write_q(tile, g, lane, CL, CH);
+  }
+  __syncthreads();
+  // ---- high layout: inverse levels 4.. -> coefficients M
+  uint32_t ML[16], MH[16];
+  hi_read_q<K>(tile, g, lane, ML, MH);
+  hi_levels<K, true, true, 0, 0, kEncPrio>(T, VP, 0, ML, MH);
+#pragma unroll
+  for (int q = 0; q < 16; ++q) asm volatile("" : "+v"(ML[q]), "+v"(MH[q]));  // materialise M once
+
+  uint32_t PL[8], PH[8];  // top-level products of shift 1, then of shifts 1 ^ 2 (fwd_top)
+  auto shift = [&](auto shc, uint32_t sh) __attribute__((always_inline)) {
+    constexpr int SH = decltype(shc)::value;
+    const uint32_t index = sh * K;
+    uint32_t XL[16], XH[16];
+    const uint32_t* vp = VP + (resident ? sh : (sh & 1u)) * G::kVPWords;
+    shift_hi<K, SH>(T, vp, index, ML, MH, XL, XH, PL, PH);
+    __syncthreads();  // the previous cq pass is done with the tile and with the other table buffer
+    if (!resident && sh + 1 < nshift && (sh + 1) * K < wanted_n)
+      stage_vpools<K, G::kThreads>(T, (sh + 1) * K, VP + ((sh + 1) & 1u) * G::kVPWords, sh + 1 < 4,
+                                   enc_conv(K, sh + 1));
+    hi_write_q<K>(tile, g, lane, XL, XH);
+    __syncthreads();
+    cq_read_q(tile, g, lane, XL, XH);
+    shift_cq<K, SH>(T, vp, index, g, XL, XH);
+    store_rows(out, shard_len, index + 16 * g, wanted_n, XL, XH, lane, ncols, full, nt);
+  };
+  if (nshift > 1 && K < wanted_n) shift(Int<1>{}, 1);
+  if (nshift > 2 && 2 * K < wanted_n) shift(Int<2>{}, 2);
+  if (nshift > 3 && 3 * K < wanted_n) shift(Int<3>{}, 3);
+#pragma unroll 1
+  for (uint32_t sh = 4; sh < nshift && sh * K < wanted_n; ++sh) shift(Int<0>{}, sh);
+}
+
+// One workgroup: one 256-column tile of one item, decoded as k_reconstruct_fast
+// decodes it (rec_tile; rec_tiles with one tile at K = 256), from the rows the
+// item's prefix record names.  Instances by SERVE as k_reconstruct_fast's.
+template <int K, int NQ, int SERVE>
+__global__ __launch_bounds__(4 * K) __attribute__((amdgpu_waves_per_eu(4))) void k_reconstruct_ragged(DevTables T, RaggedArgs r) {
+  constexpr int N = NQ * K;
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+#if NP_BOUNDS_CHECK
+  bounds_arm(bounds_of_ragged(r, T, true));
+#endif
+  const RaggedHead h = ragged_head(r);
+  if (h.item == kRaggedNoItem) return;  // padding of the plan
+  // the item as a batch of one at stride 0
+  ReconstructArgs a{};
+  a.shards = reinterpret_cast<const uint8_t*>(h.shards);
+  a.shard_len = h.shard_len;
+  a.batch = 1;
+  a.n = N;
+  a.k = K;
+  a.out = reinterpret_cast<uint8_t*>(h.data);
+  const uint32_t nsyms = static_cast<uint32_t>(h.shard_len / 2);
+  const uint8_t* pres = r.present + static_cast<size_t>(h.item) * N;
+  const uint8_t* rec = NP_BCHK(r.prefix + static_cast<size_t>(h.item) * prefix_stride_c(N, K), 2, kBkRecords);
+  const int nq = uniform(rec[0]);
+  const uint32_t occ = uniform(rec[1]);  // segments with a present row
+  const uint32_t* rows = reinterpret_cast<const uint32_t*>(rec + prefix_pools_offset(N));
+  if constexpr (kMultiTile<K>) {
+    if constexpr (SERVE >= 4) {
+      if (nq == SERVE) rec_tiles<K, SERVE>(T, a, pres, rows, smem, 0, h.tile, 1, nsyms, occ);
+    } else if (nq == 1) {
+      rec_tiles<K, 1>(T, a, pres, rows, smem, 0, h.tile, 1, nsyms, occ);
+    } else if (NQ <= 4 && nq == 2) {
+      rec_tiles<K, 2>(T, a, pres, rows, smem, 0, h.tile, 1, nsyms, occ);
+    }
+  } else {
+    const uint32_t col0 = h.tile * kTile;
+    const uint32_t ncols = min(static_cast<uint32_t>(kTile), nsyms - col0);
+    const uint8_t* sh = a.shards + 2 * static_cast<size_t>(col0);
+    const bool full = ncols == kTile && rows_vec_ok(a.shards, 0, a.shard_len);
+    if constexpr (SERVE >= 4) {
+      if (nq == SERVE) rec_tile<K, SERVE>(T, a, sh, pres, rows, smem, 0, col0, ncols, full, nullptr, occ);
+    } else if (nq == 1) {
+      rec_tile<K, 1>(T, a, sh, pres, rows, smem, 0, col0, ncols, full, nullptr, occ);
+    } else if (NQ <= 4 && nq == 2) {
+      rec_tile<K, 2>(T, a, sh, pres, rows, smem, 0, col0, ncols, full, nullptr, occ);
+    }
+  }
+}
+
+template <int K>
+hipError_t launch_encode_ragged_k(const DevTables& T, const RaggedArgs& r, hipStream_t s) {
+  k_encode_ragged<K><<<r.nblocks, Geo<K>::kThreads, encode_lds_bytes<K>(), s>>>(T, r);
+  return hipGetLastError();
+}
+
+template <int K, int NQ>
+hipError_t launch_reconstruct_ragged_k(const DevTables& T, const RaggedArgs& r, hipStream_t s) {
+  k_reconstruct_ragged<K, NQ, 2><<<r.nblocks, Geo<K>::kThreads, reconstruct_lds_bytes<K, NQ>(), s>>>(T, r);
+  if constexpr (NQ >= 4)
+    k_reconstruct_ragged<K, NQ, NQ><<<r.nblocks, Geo<K>::kThreads, reconstruct_lds_bytes<K, NQ>(), s>>>(T, r);
+  return hipGetLastError();
+}
+
+template <int K>
+hipError_t launch_reconstruct_ragged_nq(const DevTables& T, const RaggedArgs& r, hipStream_t s) {
+  if (r.n == 8u * K) return launch_reconstruct_ragged_k<K, 8>(T, r, s);
+  if (r.n == 4u * K) return launch_reconstruct_ragged_k<K, 4>(T, r, s);
+  return launch_reconstruct_ragged_k<K, 2>(T, r, s);
+}
+
+template <int K>
+void configure_ragged_k(hipError_t& e) {
+  auto set = [&](const void* f, size_t bytes) {
+    hipError_t x = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
+    if (x != hipSuccess && e == hipSuccess) e = x;
+  };
+  set(reinterpret_cast<const void*>(&k_encode_ragged<K>), encode_lds_bytes<K>());
+  set(reinterpret_cast<const void*>(&k_reconstruct_ragged<K, 2, 2>), reconstruct_lds_bytes<K, 2>());
+  set(reinterpret_cast<const void*>(&k_reconstruct_ragged<K, 4, 2>), reconstruct_lds_bytes<K, 4>());
+  set(reinterpret_cast<const void*>(&k_reconstruct_ragged<K, 4, 4>), reconstruct_lds_bytes<K, 4>());
+  set(reinterpret_cast<const void*>(&k_reconstruct_ragged<K, 8, 2>), reconstruct_lds_bytes<K, 8>());
+  set(reinterpret_cast<const void*>(&k_reconstruct_ragged<K, 8, 8>), reconstruct_lds_bytes<K, 8>());
+}
+
+hipError_t configure_ragged_kernels() {
+  hipError_t e = hipSuccess;
+  configure_ragged_k<64>(e);
+  configure_ragged_k<128>(e);
+  configure_ragged_k<256>(e);
+  return e;
+}
+
+}  // namespace
+
+bool ragged_encode_supported(uint32_t n, uint32_t k) {
+  return (k == 64 || k == 128 || k == 256) && n >= 2 * k && n <= 65536;
+}
+
+bool ragged_reconstruct_supported(uint32_t n, uint32_t k) {
+  return (k == 64 || k == 128 || k == 256) && (n == 2 * k || n == 4 * k || n == 8 * k);
+}
+
+hipError_t launch_encode_ragged(const DevTables& T, const RaggedArgs& r, hipStream_t s) {
+  if (r.nblocks == 0) return hipSuccess;
+  if (r.nblocks > 0x7fffffffu) return hipErrorInvalidValue;
+  switch (r.k) {
+    case 64: return launch_encode_ragged_k<64>(T, r, s);
+    case 128: return launch_encode_ragged_k<128>(T, r, s);
+    case 256: return launch_encode_ragged_k<256>(T, r, s);
+    default: return hipErrorNotSupported;
+  }
+}
+
+hipError_t launch_reconstruct_ragged(const DevTables& T, const RaggedArgs& r, hipStream_t s) {
+  if (r.nblocks == 0) return hipSuccess;
+  if (r.nblocks > 0x7fffffffu) return hipErrorInvalidValue;
+  switch (r.k) {
+    case 64: return launch_reconstruct_ragged_nq<64>(T, r, s);
+    case 128: return launch_reconstruct_ragged_nq<128>(T, r, s);
+    case 256: return launch_reconstruct_ragged_nq<256>(T, r, s);
     default: return hipErrorNotSupported;
   }
 }

@@ -221,4 +221,40 @@ hipError_t launch_compare_present_rows(const uint8_t* enc, size_t estride, const
 // counts[b] = number of set flags of payload b, UINT32_MAX when status[2 b] != 0.
 hipError_t launch_verify_summary(const uint8_t* flags, const uint32_t* status, uint32_t n, size_t batch,
                                  uint32_t* counts, hipStream_t s);
+
+// ---- ragged batches (np_encode_ragged_dev / np_reconstruct_ragged_dev) ----
+// Per-item device record, read with scalar loads by the workgroups of the item:
+// absolute device addresses, the engine adds the caller's bases to the offsets
+// of np_ragged_item.
+struct RaggedRec {
+  uint64_t data;       // encode: the payload; reconstruct: the output
+  uint64_t data_len;   // encode: payload bytes; reconstruct: unused
+  uint64_t shards;     // row 0; row v at shards + v * shard_len
+  uint64_t shard_len;  // bytes per row, even
+};
+// No-op entry of the block table (padding of an XCD residue that ran out).
+constexpr uint32_t kRaggedNoItem = 0xffffffffu;
+struct RaggedArgs {
+  const RaggedRec* recs;       // device, nitems
+  const uint32_t* block_item;  // device, nblocks: item of workgroup i, or kRaggedNoItem
+  const uint32_t* block_tile;  // device, nblocks: its 256-column tile of that item (behind block_item in one allocation)
+  uint32_t nitems, nblocks;
+  uint32_t n, k, wanted_n;
+  // reconstruct only: per item at their fixed strides, as ReconstructArgs
+  const uint8_t* present;  // device, nitems x n
+  const uint8_t* prefix;   // the records of launch_prefix_locator
+  const uint32_t* status;  // device, nitems x {status, have} (checked builds: its extent)
+  // the caller's buffers (checked builds arm these extents)
+  const uint8_t* data_base;
+  size_t data_size;
+  const uint8_t* shards_base;
+  size_t shards_size;
+};
+// k in {64, 128, 256}: every n of the fast encode; n / k in {2, 4, 8} for the reconstruct.
+bool ragged_encode_supported(uint32_t n, uint32_t k);
+bool ragged_reconstruct_supported(uint32_t n, uint32_t k);
+// One workgroup per block-table entry, one tile each (k_encode_fast's / the
+// single-tile k_reconstruct_fast's flow with everything per launch read per item).
+hipError_t launch_encode_ragged(const DevTables& T, const RaggedArgs& r, hipStream_t s);
+hipError_t launch_reconstruct_ragged(const DevTables& T, const RaggedArgs& r, hipStream_t s);
 }  // namespace np

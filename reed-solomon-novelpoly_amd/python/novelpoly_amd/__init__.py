@@ -35,6 +35,14 @@ class _Params(C.Structure):
     _fields_ = [("n", _sz), ("k", _sz), ("wanted_n", _sz)]
 
 
+class RaggedItem(C.Structure):
+    """np_ragged_item: one payload of a ragged device batch (offsets into the
+    caller's buffers, lengths in bytes)."""
+
+    _fields_ = [("payload_off", C.c_uint64), ("payload_len", C.c_uint64), ("shards_off", C.c_uint64),
+                ("shard_len", C.c_uint64)]
+
+
 def lib() -> C.CDLL:
     """Load libnovelpoly_hip.so (fails loudly if it was not built)."""
     global _lib
@@ -76,6 +84,10 @@ def lib() -> C.CDLL:
             "np_rs_restore_shards": (C.c_int, [vp, P, C.POINTER(vp), C.POINTER(_sz), _sz, C.POINTER(vp), _sz]),
             "np_verify_shards_batch_dev": (C.c_int, [vp, P, vp, _sz, _sz, vp, _sz, vp, vp, vp, vp]),
             "np_rs_verify_shards": (C.c_int, [vp, P, C.POINTER(vp), C.POINTER(_sz), _sz, C.POINTER(_sz), vp]),
+            "np_encode_ragged_dev": (C.c_int, [vp, P, vp, _sz, vp, _sz, C.POINTER(RaggedItem), _sz, vp]),
+            "np_reconstruct_ragged_dev": (C.c_int, [vp, P, vp, _sz, vp, vp, _sz, C.POINTER(RaggedItem), _sz, vp, vp]),
+            "np_ragged_plan": (C.c_int, [P, C.POINTER(RaggedItem), _sz, C.c_int, _sz, _sz, C.POINTER(C.c_uint32),
+                                         C.POINTER(C.c_uint32), _sz, C.POINTER(_sz)]),
             "np_error_locator_dev": (C.c_int, [vp, _sz, vp, _sz, vp, vp]),
             "np_reconstruct_from_systematic_batch_dev": (C.c_int, [vp, P, vp, _sz, _sz, _sz, vp, _sz, vp]),
             "np_encode_batch_host": (C.c_int, [vp, P, vp, _sz, _sz, _sz, vp, _sz]),
@@ -530,6 +542,69 @@ def verify_shards_batch_dev(params: CodeParams, d_shards: int, shard_len: int, b
                                             stream or None))
 
 
+NO_ITEM = 0xFFFFFFFF  # block_item of a padding workgroup of ragged_plan
+
+
+def _ragged_array(items):
+    """A ctypes array of RaggedItem from RaggedItem objects or 4-tuples
+    (payload_off, payload_len, shards_off, shard_len); an array made by
+    :func:`ragged_items` is passed through."""
+    if isinstance(items, C.Array) and items._type_ is RaggedItem:
+        return items
+    arr = (RaggedItem * max(1, len(items)))()
+    for i, it in enumerate(items):
+        arr[i] = it if isinstance(it, RaggedItem) else RaggedItem(*(int(x) for x in it))
+    return arr
+
+
+def ragged_items(items):
+    """The items as the ctypes array the ragged calls take (a caller that makes
+    several calls with one batch converts it once)."""
+    assert len(items) > 0
+    return _ragged_array(items)
+
+
+def encode_ragged_dev(params: CodeParams, d_payloads: int, payloads_size: int, d_shards: int, shards_size: int,
+                      items, ctx: Optional[Context] = None, stream: int = 0) -> None:
+    """One encode call for payloads of different lengths (np_encode_ragged_dev):
+    item b's payload at ``d_payloads + payload_off``, its row v at ``d_shards +
+    shards_off + v * shard_len``; equal to :func:`encode_batch_dev` with batch 1
+    per item.  ``items``: RaggedItem objects or 4-tuples, read before the call
+    returns."""
+    ctx = ctx or default_context()
+    _raise(lib().np_encode_ragged_dev(ctx.handle, C.byref(params._c()), d_payloads or None, payloads_size,
+                                      d_shards or None, shards_size, _ragged_array(items), len(items),
+                                      stream or None))
+
+
+def reconstruct_ragged_dev(params: CodeParams, d_shards: int, shards_size: int, d_present: int, d_out: int,
+                           out_size: int, items, ctx: Optional[Context] = None, stream: int = 0,
+                           d_status: int = 0) -> None:
+    """One reconstruct call for shards of different lengths
+    (np_reconstruct_ragged_dev): item b decodes into ``d_out + payload_off``
+    as :func:`reconstruct_batch_dev2` with batch 1 and no caller locators does;
+    ``d_present``: ``len(items) x n`` device flags."""
+    ctx = ctx or default_context()
+    _raise(lib().np_reconstruct_ragged_dev(ctx.handle, C.byref(params._c()), d_shards or None, shards_size,
+                                           d_present or None, d_out or None, out_size, _ragged_array(items),
+                                           len(items), d_status or None, stream or None))
+
+
+def ragged_plan(params: CodeParams, items, reconstruct: bool, payloads_size: int, shards_size: int):
+    """np_ragged_plan (host only): validates ``items`` as the ragged calls do
+    and returns the direct path's launch plan as a list of (item, tile), one
+    per workgroup; item == NO_ITEM marks a padding workgroup."""
+    arr = _ragged_array(items)
+    nb = _sz(0)
+    _raise(lib().np_ragged_plan(C.byref(params._c()), arr, len(items), int(bool(reconstruct)), payloads_size,
+                                shards_size, None, None, 0, C.byref(nb)))
+    bi = (C.c_uint32 * max(1, nb.value))()
+    bt = (C.c_uint32 * max(1, nb.value))()
+    _raise(lib().np_ragged_plan(C.byref(params._c()), arr, len(items), int(bool(reconstruct)), payloads_size,
+                                shards_size, bi, bt, nb.value, C.byref(nb)))
+    return [(bi[i], bt[i]) for i in range(nb.value)]
+
+
 def payload_errors(params: CodeParams, status_pairs) -> List[Optional[Error]]:
     """np_payload_status entries (a sequence of (status, have) pairs, e.g. a
     ``batch x 2`` int array copied to the host) as the crate's per-call result:
@@ -665,7 +740,7 @@ def version() -> str:
 
 
 # ----------------------------------------------------------- diagnostics ----
-BOUNDS_KINDS = ("shards", "present", "locators", "records", "out", "status", "zeros", "payloads")
+BOUNDS_KINDS = ("shards", "present", "locators", "records", "out", "status", "zeros", "payloads", "items", "blocks")
 
 
 def debug_bounds_check(ctx: Optional[Context] = None) -> Optional[dict]:
