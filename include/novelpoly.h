@@ -274,8 +274,9 @@ int np_verify_shards_batch_dev(np_ctx* ctx, const np_code_params* params, const 
  * reconstruct of its shards.  `items` is HOST memory, read before the call
  * returns and never referenced afterwards. */
 typedef struct np_ragged_item {
-  uint64_t payload_off; /* encode: payload at d_payloads + payload_off; reconstruct: output at d_out + payload_off */
-  uint64_t payload_len; /* encode: bytes, > 0.  reconstruct: ignored */
+  uint64_t payload_off; /* encode: payload at d_payloads + payload_off; reconstruct: output at d_out + payload_off;
+                           restore / verify: ignored, not validated */
+  uint64_t payload_len; /* encode: bytes, > 0.  reconstruct: ignored.  restore / verify: ignored, not validated */
   uint64_t shards_off;  /* row v of this item at d_shards + shards_off + v * shard_len */
   uint64_t shard_len;   /* bytes per row, even, > 0; encode: must equal np_shard_len(params, payload_len) */
 } np_ragged_item;
@@ -311,8 +312,41 @@ int np_encode_ragged_dev(np_ctx* ctx, const np_code_params* params, const uint8_
 int np_reconstruct_ragged_dev(np_ctx* ctx, const np_code_params* params, const uint8_t* d_shards, size_t shards_size,
                               const uint8_t* d_present, uint8_t* d_out, size_t out_size,
                               const np_ragged_item* items, size_t batch, np_payload_status* d_status, void* stream);
-/* Pure host code, no device needed: validates `items` exactly as the two calls
- * above do (reconstruct != 0: as np_reconstruct_ragged_dev, payloads_size being
+/* Restore and verify on a ragged buffer, with the item array that served the
+ * encode.  Item b is np_restore_shards_batch_dev / np_verify_shards_batch_dev
+ * with batch = 1, bit for bit, on rows d_shards + shards_off + v * shard_len,
+ * presence row b of d_present (batch rows of n bytes) and entry b of d_status,
+ * d_bad_rows and d_mismatch (batch rows of n bytes; it and d_status may be
+ * NULL, d_bad_rows is required).  Everything those calls document carries
+ * over: the restore writes only the absent rows below wanted_n of items that
+ * decode, the rows of encode(reconstruct(received)), and no other byte of
+ * d_shards; the verify only reads d_shards; NeedMoreShards items are left
+ * untouched (UINT32_MAX and an all-zero map); d_bad_rows is counted from the
+ * flags.  payload_off and payload_len are ignored and not validated.
+ * Overlapping shard ranges between items are undefined for the restore.
+ * Validation, all on the host before any launch and in this order: params and
+ * items (an odd or zero shard_len -> NP_ERR_EMPTY_SHARD; NP_ERR_INVALID_ARGUMENT
+ * for an odd shards_off or shards_off + n * shard_len past shards_size, the
+ * rest as np_reconstruct_ragged_dev without the output extent); a NULL ctx ->
+ * NP_ERR_INVALID_ARGUMENT; batch == 0 -> NP_OK, nothing launched; NULL
+ * d_shards, d_present or (verify) d_bad_rows -> NP_ERR_INVALID_ARGUMENT.
+ * Asynchronous on `stream`; the stream is not synchronised and `items` is not
+ * referenced after the call returns.
+ * k in {64, 128, 256} with n / k in {2, 4, 8}: per slice of the batch (the
+ * decoded payloads of a slice fit the restore scratch, item boundaries) the
+ * ragged reconstruct into context scratch, then the row-masked / comparing
+ * encode, one workgroup per item and 256-column tile.  Every other shape:
+ * maximal runs of consecutive items with equal shard_len at a constant spacing
+ * go as one uniform call, anything else one item per call -- correct, and slow
+ * for many distinct lengths. */
+int np_restore_shards_ragged_dev(np_ctx* ctx, const np_code_params* params, uint8_t* d_shards, size_t shards_size,
+                                 const uint8_t* d_present, const np_ragged_item* items, size_t batch,
+                                 np_payload_status* d_status, void* stream);
+int np_verify_shards_ragged_dev(np_ctx* ctx, const np_code_params* params, const uint8_t* d_shards, size_t shards_size,
+                                const uint8_t* d_present, const np_ragged_item* items, size_t batch,
+                                uint32_t* d_bad_rows, uint8_t* d_mismatch, np_payload_status* d_status, void* stream);
+/* Pure host code, no device needed: validates `items` exactly as the encode and
+ * the reconstruct above do (reconstruct != 0: as np_reconstruct_ragged_dev, payloads_size being
  * its out_size) and returns the launch plan of the direct path: *nblocks
  * workgroups, workgroup i working on tile block_tile[i] (256 columns) of item
  * block_item[i].  Every (item, tile) occurs exactly once; all workgroups of an

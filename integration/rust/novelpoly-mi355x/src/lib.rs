@@ -452,6 +452,70 @@ impl ReedSolomon {
 			stream,
 		))
 	}
+
+	/// np_restore_shards_ragged_dev: writes every item's absent rows below
+	/// `wanted_n` into `d_shards` (the rows of `encode(reconstruct(received))`),
+	/// with the items that served the encode (`payload_off` / `payload_len`
+	/// ignored); `d_status` may be null.  Asynchronous on `stream`.
+	///
+	/// # Safety
+	/// As `encode_ragged_dev`, for `d_shards`, `d_present` and `d_status`.
+	pub unsafe fn restore_shards_ragged_dev(
+		&self,
+		d_shards: *mut u8,
+		shards_size: usize,
+		d_present: *const u8,
+		items: &[sys::np_ragged_item],
+		d_status: *mut sys::np_payload_status,
+		stream: *mut std::ffi::c_void,
+	) -> Result<()> {
+		check(sys::np_restore_shards_ragged_dev(
+			self.ctx.raw,
+			&self.params.raw,
+			d_shards,
+			shards_size,
+			d_present,
+			items.as_ptr(),
+			items.len(),
+			d_status,
+			stream,
+		))
+	}
+
+	/// np_verify_shards_ragged_dev: entry b of `d_bad_rows` (device, one u32
+	/// per item) counts item b's present rows that differ from
+	/// `encode(reconstruct(received))`, `u32::MAX` when it cannot decode;
+	/// `d_mismatch` (`items.len() * n` device bytes) and `d_status` may be null.
+	/// `d_shards` is only read.  Asynchronous on `stream`.
+	///
+	/// # Safety
+	/// As `encode_ragged_dev`, for `d_shards`, `d_present`, `d_bad_rows`,
+	/// `d_mismatch` and `d_status`.
+	pub unsafe fn verify_shards_ragged_dev(
+		&self,
+		d_shards: *const u8,
+		shards_size: usize,
+		d_present: *const u8,
+		items: &[sys::np_ragged_item],
+		d_bad_rows: *mut u32,
+		d_mismatch: *mut u8,
+		d_status: *mut sys::np_payload_status,
+		stream: *mut std::ffi::c_void,
+	) -> Result<()> {
+		check(sys::np_verify_shards_ragged_dev(
+			self.ctx.raw,
+			&self.params.raw,
+			d_shards,
+			shards_size,
+			d_present,
+			items.as_ptr(),
+			items.len(),
+			d_bad_rows,
+			d_mismatch,
+			d_status,
+			stream,
+		))
+	}
 }
 
 /// encode.rs:6-11: derives (n, k) from the validator count like the crate.

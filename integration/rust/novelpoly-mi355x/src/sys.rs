@@ -175,6 +175,30 @@ extern "C" {
 		d_status: *mut np_payload_status,
 		stream: *mut c_void,
 	) -> c_int;
+	pub fn np_restore_shards_ragged_dev(
+		ctx: *mut np_ctx,
+		params: *const np_code_params,
+		d_shards: *mut u8,
+		shards_size: usize,
+		d_present: *const u8,
+		items: *const np_ragged_item,
+		batch: usize,
+		d_status: *mut np_payload_status,
+		stream: *mut c_void,
+	) -> c_int;
+	pub fn np_verify_shards_ragged_dev(
+		ctx: *mut np_ctx,
+		params: *const np_code_params,
+		d_shards: *const u8,
+		shards_size: usize,
+		d_present: *const u8,
+		items: *const np_ragged_item,
+		batch: usize,
+		d_bad_rows: *mut u32,
+		d_mismatch: *mut u8,
+		d_status: *mut np_payload_status,
+		stream: *mut c_void,
+	) -> c_int;
 	pub fn np_ragged_plan(
 		params: *const np_code_params,
 		items: *const np_ragged_item,

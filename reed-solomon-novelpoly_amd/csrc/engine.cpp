@@ -1901,6 +1901,9 @@ int np_reconstruct_from_systematic_batch_dev(np_ctx* c, const np_code_params* p,
 // table through pinned staging into context scratch, and launches the ragged
 // kernels of kernels_fast.hip.  Every other shape: runs of equal items at a
 // constant spacing through the uniform launch_encode / launch_reconstruct.
+// np_restore_shards_ragged_dev / np_verify_shards_ragged_dev run
+// the ragged reconstruct into the restore scratch and the ragged masked /
+// verify encode on the same records, in slices of the batch.
 namespace {
 
 constexpr size_t kRaggedTile = 256;  // columns per workgroup (kernels_fast.hip kTile)
@@ -2165,6 +2168,216 @@ hipError_t launch_reconstruct_ragged_all(np_ctx* c, const np_code_params* p, con
   return hipSuccess;
 }
 
+// The validation of np_restore_shards_ragged_dev / np_verify_shards_ragged_dev:
+// ragged_validate's for the reconstruct without the output extent (payload_off
+// and payload_len are not looked at).
+int ragged_masked_validate(const np_code_params* p, const np_ragged_item* items, size_t batch, size_t shards_size) {
+  int st = check_params(p);
+  if (st) return st;
+  if (batch && !items) return fail(NP_ERR_INVALID_ARGUMENT);
+  if (batch >= 0xffffffffu) return fail(NP_ERR_INVALID_ARGUMENT, batch);
+  const uint64_t rows = p->n;
+  for (size_t b = 0; b < batch; ++b) {
+    const np_ragged_item& it = items[b];
+    if (it.shard_len == 0 || (it.shard_len & 1)) return fail(NP_ERR_EMPTY_SHARD, b);
+    if (it.shards_off & 1) return fail(NP_ERR_INVALID_ARGUMENT, b);
+    const uint64_t cols = it.shard_len / 2;
+    if (cols > 0xffffffffu) return fail(NP_ERR_INVALID_ARGUMENT, b);
+    if (rows && it.shard_len > UINT64_MAX / rows) return fail(NP_ERR_INVALID_ARGUMENT, b);
+    if (past(it.shards_off, rows * it.shard_len, shards_size)) return fail(NP_ERR_INVALID_ARGUMENT, b);
+    if (cols > UINT64_MAX / (2 * p->k)) return fail(NP_ERR_INVALID_ARGUMENT, b);  // the decoded payload's bytes
+  }
+  return NP_OK;
+}
+
+// The end of the run of items starting at b0 that one uniform restore / verify
+// serves: equal shard_len, shards_off advancing by one constant stride no
+// smaller than n * shard_len.  (ragged_run also breaks on the payload fields,
+// which these calls ignore.)
+size_t ragged_shard_run(const np_ragged_item* items, size_t b0, size_t batch, uint64_t rows, uint64_t* sstride) {
+  const np_ragged_item& a = items[b0];
+  *sstride = rows * a.shard_len;
+  size_t e = b0 + 1;
+  for (; e < batch; ++e) {
+    const np_ragged_item &x = items[e], &prev = items[e - 1];
+    if (x.shard_len != a.shard_len || x.shards_off <= prev.shards_off) break;
+    const uint64_t ds = x.shards_off - prev.shards_off;
+    if (e == b0 + 1) {
+      if (ds < rows * a.shard_len) break;
+      *sstride = ds;
+    } else if (ds != *sstride) {
+      break;
+    }
+  }
+  return e;
+}
+
+// One slice of a direct ragged restore / verify: items [b0, b0 + cnt) decoded
+// into the restore scratch, with everything both masked launches share.
+struct RaggedMaskedSlice {
+  size_t cnt = 0;
+  uint8_t* scr = nullptr;  // the restore scratch: payloads, plan, status, flags
+  size_t o_plan = 0, o_status = 0, o_flags = 0;
+  np::RaggedArgs r{};
+  uint32_t* plan = nullptr;
+};
+
+// Items [b0, b0 + cnt) of a direct shape: the slice ends at the item that would
+// take the decoded payloads (each at a 256-aligned offset) past restore_cap, or
+// the prefix records past big_cap; at least one item.
+size_t ragged_masked_slice_end(const np_ctx* c, const np_code_params* p, const np_ragged_item* items, size_t b0,
+                               size_t batch, size_t per_records) {
+  size_t bytes = 0, e = b0;
+  for (; e < batch && e - b0 < per_records; ++e) {
+    const size_t pay = align256((items[e].shard_len / 2) * 2 * p->k);
+    if (e > b0 && (pay > c->restore_cap || bytes > c->restore_cap - pay)) break;
+    bytes += pay;
+  }
+  return e;
+}
+
+// Reconstructs the slice's items into the restore scratch (the ragged
+// reconstruct with records {scratch address, (shard_len / 2) * 2k, row 0,
+// shard_len}) and leaves in *sl what the masked launches take.  `own_flags`:
+// bytes per item of a flag map of the call's own (verify without d_mismatch).
+hipError_t ragged_masked_reconstruct(np_ctx* c, const np_code_params* p, const uint8_t* d_shards, size_t shards_size,
+                                     const uint8_t* d_present, const np_ragged_item* items, size_t b0, size_t cnt,
+                                     uint32_t* d_status, size_t own_flags, hipStream_t s, RaggedMaskedSlice* sl) {
+  const uint32_t n = static_cast<uint32_t>(p->n), k = static_cast<uint32_t>(p->k);
+  const size_t own_status = d_status ? 0 : kStatusBytes;
+  const size_t stride = np::prefix_stride(n, k);
+  const size_t plan_len = np::restore_plan_words(n, k) * sizeof(uint32_t);
+  std::vector<np::RaggedRec> recs(cnt);
+  size_t pay_bytes = 0;
+  for (size_t i = 0; i < cnt; ++i) {
+    const np_ragged_item& it = items[b0 + i];
+    const size_t pay = (it.shard_len / 2) * 2 * p->k;
+    recs[i] = np::RaggedRec{pay_bytes, pay, reinterpret_cast<uint64_t>(d_shards) + it.shards_off, it.shard_len};
+    pay_bytes += align256(pay);
+  }
+  sl->cnt = cnt;
+  sl->o_plan = pay_bytes;
+  sl->o_status = sl->o_plan + align256(cnt * plan_len);
+  sl->o_flags = sl->o_status + align256(cnt * own_status);
+  hipError_t e = restore_scratch(c, sl->o_flags + align256(cnt * own_flags), s, &sl->scr);
+  if (e != hipSuccess) return e;
+  for (np::RaggedRec& rec : recs) rec.data += reinterpret_cast<uint64_t>(sl->scr);
+  sl->plan = reinterpret_cast<uint32_t*>(sl->scr + sl->o_plan);
+  uint8_t* pre = nullptr;
+  size_t bytes = 0;
+  e = big_scratch(c, cnt * stride, s, &pre, &bytes);
+  np::ReconstructArgs a{};
+  a.locators = nullptr;  // computed on the device
+  a.n = n;
+  a.k = k;
+  a.present = d_present + b0 * p->n;
+  a.batch = cnt;
+  a.status = d_status ? d_status + 2 * b0 : reinterpret_cast<uint32_t*>(sl->scr + sl->o_status);
+  if (e == hipSuccess) e = HIP(np::launch_prefix_locator(c->T, a, pre, s));
+  std::vector<uint32_t> bi, bt;
+  size_t nblocks = 0;
+  ragged_plan(items, b0, cnt, &bi, &bt, &nblocks);
+  sl->r = ragged_args(p, sl->scr, sl->o_plan, d_shards, shards_size);
+  sl->r.present = a.present;
+  sl->r.prefix = pre;
+  sl->r.status = a.status;
+  if (e == hipSuccess) e = ragged_upload(c, recs, bi, bt, s, &sl->r);
+  if (e == hipSuccess) e = HIP(np::launch_reconstruct_ragged(c->T, sl->r, s));
+  return e;
+}
+
+// The three orderings behind a slice: the prefix records, the item records and
+// the restore scratch.
+hipError_t ragged_masked_done(np_ctx* c, hipStream_t s, hipError_t e) {
+  e = big_done(c, s, e);
+  e = ragged_done(c, s, e);
+  if (e != hipSuccess) return e;
+  c->restore_used = true;
+  return HIP(hipEventRecord(c->restore_done, s));
+}
+
+// np_restore_shards_ragged_dev after validation.  Direct shapes, per slice: the
+// ragged reconstruct into the restore scratch, the restore plan of the slice's
+// items, and the ragged masked encode straight into d_shards on the same
+// records and block table.  Every other shape: runs of equally long items at a
+// constant spacing through launch_restore.  Caller holds the context lock.
+hipError_t launch_restore_ragged_all(np_ctx* c, const np_code_params* p, uint8_t* d_shards, size_t shards_size,
+                                     const uint8_t* d_present, const np_ragged_item* items, size_t batch,
+                                     uint32_t* d_status, hipStream_t s) {
+  const uint32_t n = static_cast<uint32_t>(p->n), k = static_cast<uint32_t>(p->k);
+  const uint32_t wanted_n = static_cast<uint32_t>(p->wanted_n);
+  if (np::ragged_masked_supported(n, k)) {
+    const size_t per = std::max<size_t>(1, c->big_cap / np::prefix_stride(n, k));
+    for (size_t b0 = 0; b0 < batch;) {
+      const size_t b1 = ragged_masked_slice_end(c, p, items, b0, batch, per);
+      RaggedMaskedSlice sl;
+      hipError_t e = ragged_masked_reconstruct(c, p, d_shards, shards_size, d_present, items, b0, b1 - b0, d_status, 0,
+                                               s, &sl);
+      if (e == hipSuccess && wanted_n) {
+        e = HIP(np::launch_restore_plan(sl.r.present, sl.r.status, n, k, wanted_n, sl.cnt, sl.plan, s));
+        if (e == hipSuccess) e = HIP(np::launch_encode_masked_ragged(c->T, sl.r, sl.plan, s));
+      }
+      e = ragged_masked_done(c, s, e);
+      if (e != hipSuccess) return e;
+      b0 = b1;
+    }
+    return hipSuccess;
+  }
+  for (size_t b0 = 0; b0 < batch;) {
+    uint64_t bstride = 0;
+    const size_t b1 = ragged_shard_run(items, b0, batch, p->n, &bstride);
+    const np_ragged_item& it = items[b0];
+    hipError_t e = launch_restore(c, p, d_shards + it.shards_off, it.shard_len, bstride, d_present + b0 * p->n,
+                                  b1 - b0, d_status ? d_status + 2 * b0 : nullptr, s);
+    if (e != hipSuccess) return e;
+    b0 = b1;
+  }
+  return hipSuccess;
+}
+
+// np_verify_shards_ragged_dev after validation: launch_restore_ragged_all's flow
+// with the flag map zeroed, the verify plan, the ragged verify encode and the
+// count of the flags.  Caller holds the context lock.
+hipError_t launch_verify_ragged_all(np_ctx* c, const np_code_params* p, const uint8_t* d_shards, size_t shards_size,
+                                    const uint8_t* d_present, const np_ragged_item* items, size_t batch,
+                                    uint32_t* d_bad_rows, uint8_t* d_mismatch, uint32_t* d_status, hipStream_t s) {
+  const uint32_t n = static_cast<uint32_t>(p->n), k = static_cast<uint32_t>(p->k);
+  const uint32_t wanted_n = static_cast<uint32_t>(p->wanted_n);
+  if (np::ragged_masked_supported(n, k)) {
+    const size_t per = std::max<size_t>(1, c->big_cap / np::prefix_stride(n, k));
+    for (size_t b0 = 0; b0 < batch;) {
+      const size_t b1 = ragged_masked_slice_end(c, p, items, b0, batch, per);
+      RaggedMaskedSlice sl;
+      hipError_t e = ragged_masked_reconstruct(c, p, d_shards, shards_size, d_present, items, b0, b1 - b0, d_status,
+                                               d_mismatch ? 0 : p->n, s, &sl);
+      if (e == hipSuccess) {
+        uint8_t* flags = d_mismatch ? d_mismatch + b0 * p->n : sl.scr + sl.o_flags;
+        e = HIP(hipMemsetAsync(flags, 0, sl.cnt * p->n, s));
+        if (e == hipSuccess && wanted_n > k) {
+          e = HIP(np::launch_verify_plan(sl.r.present, sl.r.status, n, k, wanted_n, sl.cnt, sl.plan, s));
+          if (e == hipSuccess) e = HIP(np::launch_encode_verify_ragged(c->T, sl.r, sl.plan, flags, s));
+        }
+        if (e == hipSuccess) e = HIP(np::launch_verify_summary(flags, sl.r.status, n, sl.cnt, d_bad_rows + b0, s));
+      }
+      e = ragged_masked_done(c, s, e);
+      if (e != hipSuccess) return e;
+      b0 = b1;
+    }
+    return hipSuccess;
+  }
+  for (size_t b0 = 0; b0 < batch;) {
+    uint64_t bstride = 0;
+    const size_t b1 = ragged_shard_run(items, b0, batch, p->n, &bstride);
+    const np_ragged_item& it = items[b0];
+    hipError_t e = launch_verify(c, p, d_shards + it.shards_off, it.shard_len, bstride, d_present + b0 * p->n, b1 - b0,
+                                 d_bad_rows + b0, d_mismatch ? d_mismatch + b0 * p->n : nullptr,
+                                 d_status ? d_status + 2 * b0 : nullptr, s);
+    if (e != hipSuccess) return e;
+    b0 = b1;
+  }
+  return hipSuccess;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2214,6 +2427,36 @@ int np_reconstruct_ragged_dev(np_ctx* c, const np_code_params* p, const uint8_t*
   (void)hipSetDevice(c->device);
   return dev_err(launch_reconstruct_ragged_all(c, p, d_shards, shards_size, d_present, d_out, out_size, items, batch,
                                                reinterpret_cast<uint32_t*>(d_status), pick(c, stream)));
+}
+
+// (Both validate the items before the context: the validation is host code and
+// is tested without a device.)
+int np_restore_shards_ragged_dev(np_ctx* c, const np_code_params* p, uint8_t* d_shards, size_t shards_size,
+                                 const uint8_t* d_present, const np_ragged_item* items, size_t batch,
+                                 np_payload_status* d_status, void* stream) {
+  int st = ragged_masked_validate(p, items, batch, shards_size);
+  if (st) return st;
+  if (!c) return fail(NP_ERR_INVALID_ARGUMENT);
+  if (batch == 0) return NP_OK;
+  if (!d_shards || !d_present) return fail(NP_ERR_INVALID_ARGUMENT);
+  std::lock_guard<std::mutex> g(c->mu);  // context scratch
+  (void)hipSetDevice(c->device);
+  return dev_err(launch_restore_ragged_all(c, p, d_shards, shards_size, d_present, items, batch,
+                                           reinterpret_cast<uint32_t*>(d_status), pick(c, stream)));
+}
+
+int np_verify_shards_ragged_dev(np_ctx* c, const np_code_params* p, const uint8_t* d_shards, size_t shards_size,
+                                const uint8_t* d_present, const np_ragged_item* items, size_t batch,
+                                uint32_t* d_bad_rows, uint8_t* d_mismatch, np_payload_status* d_status, void* stream) {
+  int st = ragged_masked_validate(p, items, batch, shards_size);
+  if (st) return st;
+  if (!c) return fail(NP_ERR_INVALID_ARGUMENT);
+  if (batch == 0) return NP_OK;
+  if (!d_shards || !d_present || !d_bad_rows) return fail(NP_ERR_INVALID_ARGUMENT);
+  std::lock_guard<std::mutex> g(c->mu);  // context scratch
+  (void)hipSetDevice(c->device);
+  return dev_err(launch_verify_ragged_all(c, p, d_shards, shards_size, d_present, items, batch, d_bad_rows,
+                                          d_mismatch, reinterpret_cast<uint32_t*>(d_status), pick(c, stream)));
 }
 
 // ------------------------------------------------------------ multi-GPU ----

@@ -1793,6 +1793,7 @@ namespace {
 hipError_t configure_masked_kernels();  // below, with the masked encode's launchers
 hipError_t configure_verify_kernels();  // with the verify encode
 hipError_t configure_ragged_kernels();  // at the end of the file, with the ragged kernels
+hipError_t configure_ragged_masked_kernels();  // behind them, with the ragged restore and verify
 }
 
 hipError_t configure_fast_kernels() {
@@ -1823,6 +1824,7 @@ hipError_t configure_fast_kernels() {
   if (e == hipSuccess) e = configure_masked_kernels();
   if (e == hipSuccess) e = configure_verify_kernels();
   if (e == hipSuccess) e = configure_ragged_kernels();
+  if (e == hipSuccess) e = configure_ragged_masked_kernels();
   return e;
 }
 
@@ -2164,7 +2166,7 @@ hipError_t launch_encode_verify(const DevTables& T, const EncodeArgs& a, const u
 // the table (kRaggedNoItem) exit, workgroup-uniformly, before any barrier of
 // the flow.  The present flags, the prefix records and the status stay per
 // item at their fixed strides.
-// The last kernels of this file: every older kernel's assembly stays what it was.
+// Behind every older kernel of this file: their assembly stays what it was.
 namespace {
 
 typedef const __attribute__((address_space(4))) uint64_t* crec_t;
@@ -2438,6 +2440,401 @@ hipError_t launch_reconstruct_ragged(const DevTables& T, const RaggedArgs& r, hi
     case 256: return launch_reconstruct_ragged_nq<256>(T, r, s);
     default: return hipErrorNotSupported;
   }
+}
+
+// ------------------------------------------- ragged restore and verify ----
+// np_restore_shards_ragged_dev / np_verify_shards_ragged_dev: the flows of
+// k_encode_masked and k_encode_verify with the ragged head.  The item's record
+// names its decoded payload in the context scratch ({address, (shard_len / 2) *
+// 2K}) and its shard rows; the plan words (k_restore_plan / k_verify_plan) and
+// the verify's flag row stay per item at their fixed strides.  `plan` and
+// `flags` are kernel parameters of their own: RaggedArgs is what the kernels
+// above take.  Every skip of the uniform kernels is kept, each exit
+// workgroup-uniform and before the barrier it would miss.
+// The last kernels of this file: every older kernel's assembly stays what it was.
+namespace {
+
+#if NP_BOUNDS_CHECK
+// bounds_of_ragged's extents (the payload scratch, the caller's shard buffer,
+// the records, the block table) plus what the engine's flow around the launch
+// holds per item: plan, present flags, status and (verify) the flag map.
+__device__ __forceinline__ BoundsSet bounds_of_ragged_masked(const RaggedArgs& r, const DevTables& T,
+                                                             const uint32_t* plan, const uint8_t* flags) {
+  BoundsSet b = bounds_of_ragged(r, T, false);
+  auto set = [&](uint32_t k, const void* p, uint64_t bytes) {
+    if (!p || bytes == 0) return;
+    b.lo[k] = reinterpret_cast<uint64_t>(p);
+    b.hi[k] = b.lo[k] + bytes;
+  };
+  set(kBkRecords, plan, static_cast<uint64_t>(r.nitems) * restore_plan_words(r.n, r.k) * 4u);
+  set(kBkPresent, r.present, static_cast<uint64_t>(r.nitems) * r.n);
+  set(kBkStatus, r.status, static_cast<uint64_t>(r.nitems) * 8u);
+  set(kBkOut, flags, static_cast<uint64_t>(r.nitems) * r.n);
+  return b;
+}
+#endif
+
+// One workgroup: one 256-column tile of one item, the rows of the item's plan
+// stored into its shard rows (k_encode_masked's flow).
+template <int K>
+__global__ __launch_bounds__(4 * K) __attribute__((amdgpu_waves_per_eu(4))) void k_encode_masked_ragged(
+    DevTables T, RaggedArgs r, const uint32_t* plan) {
+  using G = Geo<K>;
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  uint8_t* tile = smem;
+  uint32_t* VP = reinterpret_cast<uint32_t*>(smem + G::kTileBytes);  // up to 4 staged transforms
+  const uint32_t nshift = r.n / K;
+  const uint32_t segw = static_cast<uint32_t>(restore_seg_words(r.n, K));
+  const uint32_t planw = static_cast<uint32_t>(restore_plan_words(r.n, K));
+#if NP_BOUNDS_CHECK
+  bounds_arm(bounds_of_ragged_masked(r, T, plan, nullptr));
+#endif
+  const RaggedHead h = ragged_head(r);
+  if (h.item == kRaggedNoItem) return;  // padding of the plan
+  NP_BNOTE(plan + static_cast<size_t>(h.item) * planw, 4u * planw, kBkRecords);
+  const cpool_t seg = (cpool_t)(plan) + static_cast<size_t>(h.item) * planw;
+  const cpool_t rowbits = seg + segw;
+  const bool seg0 = (seg[0] & 1u) != 0;
+  const uint32_t first = next_segment(seg, 1, nshift);  // the first shift to run
+  if (!seg0 && first == nshift) return;                 // nothing to restore (or NeedMoreShards)
+  const uint8_t* pay = reinterpret_cast<const uint8_t*>(h.data);
+  const size_t payload_len = h.data_len, shard_len = h.shard_len;
+  uint8_t* const shards = reinterpret_cast<uint8_t*>(h.shards);
+  const uint32_t nchunks = static_cast<uint32_t>(shard_len / 2);
+  const uint32_t ch0 = h.tile * kTile;
+  const uint32_t ncols = min(static_cast<uint32_t>(kTile), nchunks - ch0);
+  uint8_t* out = shards + 2 * static_cast<size_t>(ch0);
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, g = uniform(tid >> 6);
+  const bool full = ncols == kTile && rows_vec_ok(shards, 0, shard_len);
+
+  // ---- tile load (as k_encode_fast)
+  {
+    const uint32_t c0 = tid / G::Q, m0 = tid % G::Q;
+    const uint32_t base = col_base<K>(c0) ^ (8u * m0);
+    const size_t gbase = static_cast<size_t>(ch0 + c0) * 2 * K + 8u * m0;
+    const bool fast = out_vec_ok(pay, 0) && static_cast<size_t>(ch0 + kTile) * 2 * K <= payload_len;
+    if (fast) {
+      uint2 v[16];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) v[i] = load_once(pay + gbase + static_cast<size_t>(i) * 32 * K);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) *reinterpret_cast<uint2*>(tile + (base ^ col_base_c<K>(16u * i))) = v[i];
+    } else {
+#pragma unroll 1
+      for (uint32_t i = 0; i < 16; ++i) {
+        const size_t g0 = gbase + static_cast<size_t>(i) * 32 * K;
+        uint32_t w[2] = {0, 0};
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (g0 + e < payload_len) w[e >> 2] |= static_cast<uint32_t>(*NP_BCHK(pay + (g0 + e), 1, kBkPayloads)) << (8 * (e & 3));
+        *reinterpret_cast<uint2*>(tile + (base ^ col_base_c<K>(16u * i))) = make_uint2(w[0], w[1]);
+      }
+    }
+  }
+  const bool nt = rows_nt(shards, 0, shard_len);
+  // n <= 4K: one table buffer per transform that runs; otherwise two buffers
+  // alternate, each shift staging the next one that runs
+  const bool resident = nshift <= 4;
+  if (first < nshift) {
+    stage_vpools<K, G::kThreads>(T, 0, VP, true);  // inverse transform, index 0
+    if (resident) {
+      for (uint32_t sh = first; sh < nshift; sh = next_segment(seg, sh + 1, nshift))
+        stage_vpools<K, G::kThreads>(T, sh * K, VP + sh * G::kVPWords, true, enc_conv_u<K>(sh));
+    } else {
+      stage_vpools<K, G::kThreads>(T, first * K, VP + G::kVPWords, uniform_b(first < 4), enc_conv_u<K>(first));
+    }
+  }
+  __syncthreads();
+
+  const uint32_t cqb = col_base<K>(4 * lane) ^ (32u * g);  // blocks 4g..4g+3 of columns 4l..4l+3
+  // ---- cq pass: absent systematic rows, inverse levels 0..3
+  {
+    uint32_t CL[16], CH[16];
+    cq_read<K>(tile, cqb, CL, CH);
+    if (seg0) store_rows_masked(out, shard_len, 16 * g, restore_mask16(rowbits, 16 * g), CL, CH, lane, ncols, full, nt);
+    if (first == nshift) return;  // no parity row to restore
+    tower_convert(T, CL, CH);     // transforms run in tower coordinates
+    cq_levels<K, true, true, 0, false, kEncPrioCq>(T, VP, 0, g, CL, CH);
+    // the quad items overlay payload blocks that other waves read: wait for
+    // every wave's cq_read
+    __syncthreads();
+    cq_write_q(tile, g, lane, CL, CH);
+  }
+  __syncthreads();
+  // ---- high layout: inverse levels 4.. -> coefficients M
+  uint32_t ML[16], MH[16];
+  hi_read_q<K>(tile, g, lane, ML, MH);
+  hi_levels<K, true, true, 0, 0, kEncPrio>(T, VP, 0, ML, MH);
+#pragma unroll
+  for (int q = 0; q < 16; ++q) asm volatile("" : "+v"(ML[q]), "+v"(MH[q]));  // materialise M once
+
+  // top-level products of shift 1, then of shifts 1 ^ 2 (fwd_top); zero, so that
+  // a shift 2 without shift 1 accumulates into defined values (which nobody reads)
+  uint32_t PL[8] = {}, PH[8] = {};
+  uint32_t slot = 1;  // !resident: the table buffer of the shift that runs
+  // shift sh; nxt: the next shift that runs (nshift: none)
+  auto shift = [&](auto shc, uint32_t sh, uint32_t nxt) __attribute__((always_inline)) {
+    constexpr int SH = decltype(shc)::value;
+    constexpr int SHC = SH == kShift3Own ? 3 : SH;
+    const uint32_t index = sh * K;
+    uint32_t XL[16], XH[16];
+    const uint32_t* vp = VP + (resident ? sh : slot) * G::kVPWords;
+    if constexpr (SH == kShift3Own) {
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        XL[q] = ML[q];
+        XH[q] = MH[q];
+      }
+      fwd_top<K, 0, 0>(T, vp, index, XL, XH, PL, PH);
+      hi_levels<K, false, false, 1, 0, kEncPrio>(T, vp, index, XL, XH);
+    } else {
+      shift_hi<K, SH>(T, vp, index, ML, MH, XL, XH, PL, PH);
+    }
+    __syncthreads();  // the previous cq pass is done with the tile and with the other table buffer
+    if (!resident && nxt < nshift)
+      stage_vpools<K, G::kThreads>(T, nxt * K, VP + (slot ^ 1u) * G::kVPWords, uniform_b(nxt < 4),
+                                   enc_conv_u<K>(nxt));
+    hi_write_q<K>(tile, g, lane, XL, XH);
+    __syncthreads();
+    cq_read_q(tile, g, lane, XL, XH);
+    const uint32_t mask = restore_mask16(rowbits, index + 16 * g);
+    shift_cq_rows<K, SHC>(T, vp, index, g, XL, XH, mask);
+    store_rows_masked(out, shard_len, index + 16 * g, mask, XL, XH, lane, ncols, full, nt);
+    slot ^= 1u;
+  };
+  const bool own3 = ((seg[0] >> 1) & 3u) != 3u;  // shift 1 or 2 skipped
+  // cur: the next shift to run; nshift (2 at n = 2K: not "shift 2") when none is left
+  uint32_t cur = first;
+  if (cur == 1) {
+    const uint32_t nxt = next_segment(seg, 2, nshift);
+    shift(Int<1>{}, 1, nxt);
+    cur = nxt;
+  }
+  if (cur == 2 && cur < nshift) {
+    const uint32_t nxt = next_segment(seg, 3, nshift);
+    shift(Int<2>{}, 2, nxt);
+    cur = nxt;
+  }
+  if (cur == 3 && cur < nshift) {
+    const uint32_t nxt = next_segment(seg, 4, nshift);
+    if (own3)
+      shift(Int<kShift3Own>{}, 3, nxt);
+    else
+      shift(Int<3>{}, 3, nxt);
+    cur = nxt;
+  }
+#pragma unroll 1
+  while (cur < nshift) {
+    const uint32_t nxt = next_segment(seg, cur + 1, nshift);
+    shift(Int<0>{}, cur, nxt);
+    cur = nxt;
+  }
+}
+
+// One workgroup: one 256-column tile of one item, the present rows of the
+// item's plan compared with its re-encoding (k_encode_verify's flow); the flag
+// row of item i is flags + i * n.  The shard rows are only read.
+template <int K>
+__global__ __launch_bounds__(4 * K) __attribute__((amdgpu_waves_per_eu(4))) void k_encode_verify_ragged(
+    DevTables T, RaggedArgs r, const uint32_t* plan, uint8_t* flags) {
+  using G = Geo<K>;
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  uint8_t* tile = smem;
+  uint32_t* VP = reinterpret_cast<uint32_t*>(smem + G::kTileBytes);  // up to 4 staged transforms
+  const uint32_t nshift = r.n / K;
+  const uint32_t segw = static_cast<uint32_t>(restore_seg_words(r.n, K));
+  const uint32_t planw = static_cast<uint32_t>(restore_plan_words(r.n, K));
+#if NP_BOUNDS_CHECK
+  bounds_arm(bounds_of_ragged_masked(r, T, plan, flags));
+#endif
+  const RaggedHead h = ragged_head(r);
+  if (h.item == kRaggedNoItem) return;  // padding of the plan
+  NP_BNOTE(plan + static_cast<size_t>(h.item) * planw, 4u * planw, kBkRecords);
+  const cpool_t seg = (cpool_t)(plan) + static_cast<size_t>(h.item) * planw;
+  const cpool_t rowbits = seg + segw;
+  const uint32_t first = next_segment(seg, 1, nshift);  // the first shift to run
+  if (first == nshift) return;                          // no row to compare (or NeedMoreShards)
+  const uint8_t* pay = reinterpret_cast<const uint8_t*>(h.data);
+  const size_t payload_len = h.data_len, shard_len = h.shard_len;
+  const uint8_t* const shards = reinterpret_cast<const uint8_t*>(h.shards);
+  const uint32_t nchunks = static_cast<uint32_t>(shard_len / 2);
+  const uint32_t ch0 = h.tile * kTile;
+  const uint32_t ncols = min(static_cast<uint32_t>(kTile), nchunks - ch0);
+  const uint8_t* in = shards + 2 * static_cast<size_t>(ch0);
+  uint8_t* flag = flags + static_cast<size_t>(h.item) * r.n;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, g = uniform(tid >> 6);
+  const bool full = ncols == kTile && rows_vec_ok(shards, 0, shard_len);
+
+  // ---- tile load (as k_encode_fast)
+  {
+    const uint32_t c0 = tid / G::Q, m0 = tid % G::Q;
+    const uint32_t base = col_base<K>(c0) ^ (8u * m0);
+    const size_t gbase = static_cast<size_t>(ch0 + c0) * 2 * K + 8u * m0;
+    const bool fast = out_vec_ok(pay, 0) && static_cast<size_t>(ch0 + kTile) * 2 * K <= payload_len;
+    if (fast) {
+      uint2 v[16];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) v[i] = load_once(pay + gbase + static_cast<size_t>(i) * 32 * K);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) *reinterpret_cast<uint2*>(tile + (base ^ col_base_c<K>(16u * i))) = v[i];
+    } else {
+#pragma unroll 1
+      for (uint32_t i = 0; i < 16; ++i) {
+        const size_t g0 = gbase + static_cast<size_t>(i) * 32 * K;
+        uint32_t w[2] = {0, 0};
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (g0 + e < payload_len) w[e >> 2] |= static_cast<uint32_t>(*NP_BCHK(pay + (g0 + e), 1, kBkPayloads)) << (8 * (e & 3));
+        *reinterpret_cast<uint2*>(tile + (base ^ col_base_c<K>(16u * i))) = make_uint2(w[0], w[1]);
+      }
+    }
+  }
+  // n <= 4K: one table buffer per transform that runs; otherwise two buffers
+  // alternate, each shift staging the next one that runs
+  const bool resident = nshift <= 4;
+  stage_vpools<K, G::kThreads>(T, 0, VP, true);  // inverse transform, index 0
+  if (resident) {
+    for (uint32_t sh = first; sh < nshift; sh = next_segment(seg, sh + 1, nshift))
+      stage_vpools<K, G::kThreads>(T, sh * K, VP + sh * G::kVPWords, true, enc_conv_u<K>(sh));
+  } else {
+    stage_vpools<K, G::kThreads>(T, first * K, VP + G::kVPWords, uniform_b(first < 4), enc_conv_u<K>(first));
+  }
+  __syncthreads();
+
+  const uint32_t cqb = col_base<K>(4 * lane) ^ (32u * g);  // blocks 4g..4g+3 of columns 4l..4l+3
+  // ---- cq pass: inverse levels 0..3
+  {
+    uint32_t CL[16], CH[16];
+    cq_read<K>(tile, cqb, CL, CH);
+    tower_convert(T, CL, CH);  // transforms run in tower coordinates
+    cq_levels<K, true, true, 0, false, kEncPrioCq>(T, VP, 0, g, CL, CH);
+    // the quad items overlay payload blocks that other waves read: wait for
+    // every wave's cq_read
+    __syncthreads();
+    cq_write_q(tile, g, lane, CL, CH);
+  }
+  __syncthreads();
+  // ---- high layout: inverse levels 4.. -> coefficients M
+  uint32_t ML[16], MH[16];
+  hi_read_q<K>(tile, g, lane, ML, MH);
+  hi_levels<K, true, true, 0, 0, kEncPrio>(T, VP, 0, ML, MH);
+#pragma unroll
+  for (int q = 0; q < 16; ++q) asm volatile("" : "+v"(ML[q]), "+v"(MH[q]));  // materialise M once
+
+  // top-level products of shift 1, then of shifts 1 ^ 2 (fwd_top); zero, so that
+  // a shift 2 without shift 1 accumulates into defined values (which nobody reads)
+  uint32_t PL[8] = {}, PH[8] = {};
+  uint32_t slot = 1;  // !resident: the table buffer of the shift that runs
+  // shift sh; nxt: the next shift that runs (nshift: none)
+  auto shift = [&](auto shc, uint32_t sh, uint32_t nxt) __attribute__((always_inline)) {
+    constexpr int SH = decltype(shc)::value;
+    constexpr int SHC = SH == kShift3Own ? 3 : SH;
+    const uint32_t index = sh * K;
+    uint32_t XL[16], XH[16];
+    const uint32_t* vp = VP + (resident ? sh : slot) * G::kVPWords;
+    if constexpr (SH == kShift3Own) {
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        XL[q] = ML[q];
+        XH[q] = MH[q];
+      }
+      fwd_top<K, 0, 0>(T, vp, index, XL, XH, PL, PH);
+      hi_levels<K, false, false, 1, 0, kEncPrio>(T, vp, index, XL, XH);
+    } else {
+      shift_hi<K, SH>(T, vp, index, ML, MH, XL, XH, PL, PH);
+    }
+    __syncthreads();  // the previous cq pass is done with the tile and with the other table buffer
+    if (!resident && nxt < nshift)
+      stage_vpools<K, G::kThreads>(T, nxt * K, VP + (slot ^ 1u) * G::kVPWords, uniform_b(nxt < 4),
+                                   enc_conv_u<K>(nxt));
+    hi_write_q<K>(tile, g, lane, XL, XH);
+    __syncthreads();
+    cq_read_q(tile, g, lane, XL, XH);
+    const uint32_t mask = restore_mask16(rowbits, index + 16 * g);
+    shift_cq_rows<K, SHC>(T, vp, index, g, XL, XH, mask);
+    compare_rows_masked(in, shard_len, index + 16 * g, mask, XL, XH, lane, ncols, full, flag);
+    slot ^= 1u;
+  };
+  const bool own3 = ((seg[0] >> 1) & 3u) != 3u;  // shift 1 or 2 skipped
+  // cur: the next shift to run; nshift (2 at n = 2K: not "shift 2") when none is left
+  uint32_t cur = first;
+  if (cur == 1) {
+    const uint32_t nxt = next_segment(seg, 2, nshift);
+    shift(Int<1>{}, 1, nxt);
+    cur = nxt;
+  }
+  if (cur == 2 && cur < nshift) {
+    const uint32_t nxt = next_segment(seg, 3, nshift);
+    shift(Int<2>{}, 2, nxt);
+    cur = nxt;
+  }
+  if (cur == 3 && cur < nshift) {
+    const uint32_t nxt = next_segment(seg, 4, nshift);
+    if (own3)
+      shift(Int<kShift3Own>{}, 3, nxt);
+    else
+      shift(Int<3>{}, 3, nxt);
+    cur = nxt;
+  }
+#pragma unroll 1
+  while (cur < nshift) {
+    const uint32_t nxt = next_segment(seg, cur + 1, nshift);
+    shift(Int<0>{}, cur, nxt);
+    cur = nxt;
+  }
+}
+
+template <int K>
+void configure_ragged_masked_k(hipError_t& e) {
+  auto set = [&](const void* f, size_t bytes) {
+    hipError_t x = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
+    if (x != hipSuccess && e == hipSuccess) e = x;
+  };
+  set(reinterpret_cast<const void*>(&k_encode_masked_ragged<K>), encode_lds_bytes<K>());
+  set(reinterpret_cast<const void*>(&k_encode_verify_ragged<K>), encode_lds_bytes<K>());
+}
+
+hipError_t configure_ragged_masked_kernels() {
+  hipError_t e = hipSuccess;
+  configure_ragged_masked_k<64>(e);
+  configure_ragged_masked_k<128>(e);
+  configure_ragged_masked_k<256>(e);
+  return e;
+}
+
+}  // namespace
+
+bool ragged_masked_supported(uint32_t n, uint32_t k) { return ragged_reconstruct_supported(n, k); }
+
+hipError_t launch_encode_masked_ragged(const DevTables& T, const RaggedArgs& r, const uint32_t* plan, hipStream_t s) {
+  if (r.nblocks == 0) return hipSuccess;
+  if (r.nblocks > 0x7fffffffu) return hipErrorInvalidValue;
+  switch (r.k) {
+    case 64: k_encode_masked_ragged<64><<<r.nblocks, Geo<64>::kThreads, encode_lds_bytes<64>(), s>>>(T, r, plan); break;
+    case 128: k_encode_masked_ragged<128><<<r.nblocks, Geo<128>::kThreads, encode_lds_bytes<128>(), s>>>(T, r, plan); break;
+    case 256: k_encode_masked_ragged<256><<<r.nblocks, Geo<256>::kThreads, encode_lds_bytes<256>(), s>>>(T, r, plan); break;
+    default: return hipErrorNotSupported;
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_encode_verify_ragged(const DevTables& T, const RaggedArgs& r, const uint32_t* plan, uint8_t* flags,
+                                       hipStream_t s) {
+  if (r.nblocks == 0) return hipSuccess;
+  if (r.nblocks > 0x7fffffffu) return hipErrorInvalidValue;
+  switch (r.k) {
+    case 64:
+      k_encode_verify_ragged<64><<<r.nblocks, Geo<64>::kThreads, encode_lds_bytes<64>(), s>>>(T, r, plan, flags);
+      break;
+    case 128:
+      k_encode_verify_ragged<128><<<r.nblocks, Geo<128>::kThreads, encode_lds_bytes<128>(), s>>>(T, r, plan, flags);
+      break;
+    case 256:
+      k_encode_verify_ragged<256><<<r.nblocks, Geo<256>::kThreads, encode_lds_bytes<256>(), s>>>(T, r, plan, flags);
+      break;
+    default: return hipErrorNotSupported;
+  }
+  return hipGetLastError();
 }
 
 }  // namespace np

@@ -257,4 +257,17 @@ bool ragged_reconstruct_supported(uint32_t n, uint32_t k);
 // single-tile k_reconstruct_fast's flow with everything per launch read per item).
 hipError_t launch_encode_ragged(const DevTables& T, const RaggedArgs& r, hipStream_t s);
 hipError_t launch_reconstruct_ragged(const DevTables& T, const RaggedArgs& r, hipStream_t s);
+
+// ---- ragged restore and verify (np_restore_shards_ragged_dev / np_verify_shards_ragged_dev) ----
+// Exactly where ragged_reconstruct_supported: the flow reconstructs first.
+bool ragged_masked_supported(uint32_t n, uint32_t k);
+// k_encode_masked's / k_encode_verify's flow per block-table entry.  The
+// records name the decoded payload of an item ({address, (shard_len / 2) * 2k})
+// and its shard rows; plan: restore_plan_words(n, k) words per item
+// (launch_restore_plan / launch_verify_plan); flags: n bytes per item.
+// r.data_base / r.data_size: the payload scratch; r.present and r.status: what
+// the plan was made from (checked builds arm their extents).
+hipError_t launch_encode_masked_ragged(const DevTables& T, const RaggedArgs& r, const uint32_t* plan, hipStream_t s);
+hipError_t launch_encode_verify_ragged(const DevTables& T, const RaggedArgs& r, const uint32_t* plan, uint8_t* flags,
+                                       hipStream_t s);
 }  // namespace np

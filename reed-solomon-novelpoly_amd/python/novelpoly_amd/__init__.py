@@ -86,6 +86,8 @@ def lib() -> C.CDLL:
             "np_rs_verify_shards": (C.c_int, [vp, P, C.POINTER(vp), C.POINTER(_sz), _sz, C.POINTER(_sz), vp]),
             "np_encode_ragged_dev": (C.c_int, [vp, P, vp, _sz, vp, _sz, C.POINTER(RaggedItem), _sz, vp]),
             "np_reconstruct_ragged_dev": (C.c_int, [vp, P, vp, _sz, vp, vp, _sz, C.POINTER(RaggedItem), _sz, vp, vp]),
+            "np_restore_shards_ragged_dev": (C.c_int, [vp, P, vp, _sz, vp, C.POINTER(RaggedItem), _sz, vp, vp]),
+            "np_verify_shards_ragged_dev": (C.c_int, [vp, P, vp, _sz, vp, C.POINTER(RaggedItem), _sz, vp, vp, vp, vp]),
             "np_ragged_plan": (C.c_int, [P, C.POINTER(RaggedItem), _sz, C.c_int, _sz, _sz, C.POINTER(C.c_uint32),
                                          C.POINTER(C.c_uint32), _sz, C.POINTER(_sz)]),
             "np_error_locator_dev": (C.c_int, [vp, _sz, vp, _sz, vp, vp]),
@@ -588,6 +590,32 @@ def reconstruct_ragged_dev(params: CodeParams, d_shards: int, shards_size: int, 
     _raise(lib().np_reconstruct_ragged_dev(ctx.handle, C.byref(params._c()), d_shards or None, shards_size,
                                            d_present or None, d_out or None, out_size, _ragged_array(items),
                                            len(items), d_status or None, stream or None))
+
+
+def restore_shards_ragged_dev(params: CodeParams, d_shards: int, shards_size: int, d_present: int, items,
+                              ctx: Optional[Context] = None, stream: int = 0, d_status: int = 0) -> None:
+    """:func:`restore_shards_batch_dev` on a ragged buffer
+    (np_restore_shards_ragged_dev): item b's absent rows below ``wanted_n`` are
+    written at ``d_shards + shards_off + v * shard_len`` as the uniform call
+    with batch 1 writes them.  The items of :func:`encode_ragged_dev` serve;
+    ``payload_off`` and ``payload_len`` are ignored."""
+    ctx = ctx or default_context()
+    _raise(lib().np_restore_shards_ragged_dev(ctx.handle, C.byref(params._c()), d_shards or None, shards_size,
+                                              d_present or None, _ragged_array(items), len(items), d_status or None,
+                                              stream or None))
+
+
+def verify_shards_ragged_dev(params: CodeParams, d_shards: int, shards_size: int, d_present: int, items,
+                             d_bad_rows: int, ctx: Optional[Context] = None, stream: int = 0, d_mismatch: int = 0,
+                             d_status: int = 0) -> None:
+    """:func:`verify_shards_batch_dev` on a ragged buffer
+    (np_verify_shards_ragged_dev): entry b of ``d_bad_rows`` (and row b of
+    ``d_mismatch``, ``len(items) x n`` bytes) is what the uniform call with
+    batch 1 gives for item b; ``d_shards`` is only read."""
+    ctx = ctx or default_context()
+    _raise(lib().np_verify_shards_ragged_dev(ctx.handle, C.byref(params._c()), d_shards or None, shards_size,
+                                             d_present or None, _ragged_array(items), len(items), d_bad_rows or None,
+                                             d_mismatch or None, d_status or None, stream or None))
 
 
 def ragged_plan(params: CodeParams, items, reconstruct: bool, payloads_size: int, shards_size: int):
