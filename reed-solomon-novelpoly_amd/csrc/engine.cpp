@@ -236,6 +236,24 @@ np::EncodeArgs enc_args(const np_code_params* p, const uint8_t* payloads, size_t
   return a;
 }
 
+// A reconstruct whose locators are computed on the device.
+np::ReconstructArgs rec_args(const np_code_params* p, const uint8_t* shards, size_t shard_len, size_t bstride,
+                             const uint8_t* present, size_t batch, uint8_t* out, size_t out_stride,
+                             uint32_t* status) {
+  np::ReconstructArgs a{};
+  a.shards = shards;
+  a.shard_len = shard_len;
+  a.batch_stride = bstride;
+  a.present = present;
+  a.batch = batch;
+  a.n = static_cast<uint32_t>(p->n);
+  a.k = static_cast<uint32_t>(p->k);
+  a.out = out;
+  a.out_stride = out_stride;
+  a.status = status;
+  return a;
+}
+
 // Bytes of big-kernel scratch per context (k = 2048 decode at n = 16384:
 // 256 slots of 9.1 MiB; the sub-transform path: 512 x 1 MiB payloads in one
 // slice at every validator count, 4.5 GiB of slots at 40,000 validators).
@@ -1378,18 +1396,9 @@ int reconstruct_dev2(np_ctx* c, const np_code_params* p, const uint8_t* d_shards
   static_assert(sizeof(np_payload_status) == 2 * sizeof(uint32_t), "status layout of ReconstructArgs::status");
   std::lock_guard<std::mutex> g(c->mu);  // context scratch
   (void)hipSetDevice(c->device);
-  np::ReconstructArgs a{};
-  a.shards = d_shards;
-  a.shard_len = shard_len;
-  a.batch_stride = bstride;
-  a.present = d_present;
+  np::ReconstructArgs a = rec_args(p, d_shards, shard_len, bstride, d_present, batch, d_out, out_stride,
+                                   reinterpret_cast<uint32_t*>(d_status));
   a.locators = d_loc;
-  a.batch = batch;
-  a.n = static_cast<uint32_t>(p->n);
-  a.k = static_cast<uint32_t>(p->k);
-  a.out = d_out;
-  a.out_stride = out_stride;
-  a.status = reinterpret_cast<uint32_t*>(d_status);
   a.trusted = trusted;
 #if NP_BOUNDS_CHECK
   if (const char* st = std::getenv("NP_BOUNDS_SELFTEST")) a.chk_shrink_out = static_cast<uint32_t>(std::atoi(st));
@@ -1416,64 +1425,93 @@ hipError_t restore_scratch(np_ctx* c, size_t want, hipStream_t s, uint8_t** out)
   return e;
 }
 
+// What a uniform restore / verify call fixes for all its slices: whether the
+// row-masked encodes serve (n, k); per payload the decoded bytes, the scratch
+// shard rows (!direct) and the plan bytes (direct); the payloads per slice.
+struct MaskedShape {
+  uint32_t n, k, wanted_n;
+  bool direct;
+  size_t pay_len, rows_len, plan_len, per;
+};
+
+MaskedShape masked_shape(const np_ctx* c, const np_code_params* p, size_t shard_len) {
+  MaskedShape m{};
+  m.n = static_cast<uint32_t>(p->n), m.k = static_cast<uint32_t>(p->k), m.wanted_n = static_cast<uint32_t>(p->wanted_n);
+  m.direct = np::masked_encode_supported(m.n, m.k);
+  m.pay_len = (shard_len / 2) * 2 * p->k;
+  m.rows_len = m.direct ? 0 : p->wanted_n * shard_len;
+  m.plan_len = m.direct ? np::restore_plan_words(m.n, m.k) * sizeof(uint32_t) : 0;
+  // The cap bounds the decoded payloads of a slice, and its scratch shard rows
+  // likewise (the plan and status come on top: bytes per payload).  Slices are
+  // multiples of 8 payloads where they can be: the fast kernels place a
+  // payload's tiles on one XCD only then (fast_common.hpp tile_of), and a slice
+  // of 1023 measured 1.5-1.7 x the reconstruct time of one of 1024.
+  m.per = c->restore_cap / std::max(m.pay_len, m.rows_len);
+  m.per = m.per >= 8 ? m.per & ~size_t(7) : std::max<size_t>(1, m.per);
+  return m;
+}
+
+// One slice of a uniform restore / verify: payloads [b0, b0 + cnt) decoded to
+// the head of the restore scratch.
+struct MaskedSlice {
+  size_t cnt = 0;
+  uint8_t *scr = nullptr, *rows = nullptr, *flags = nullptr;  // payloads; !direct: shard rows; own flag map
+  uint32_t* plan = nullptr;
+  np::ReconstructArgs a{};
+};
+
+// Lays out the scratch of the slice at b0 and reconstructs its payloads into it.
+// `own_flags`: bytes per payload of a flag map of the call's own (verify
+// without d_mismatch).
+hipError_t masked_reconstruct(np_ctx* c, const np_code_params* p, const MaskedShape& m, const uint8_t* d_shards,
+                              size_t shard_len, size_t bstride, const uint8_t* d_present, size_t b0, size_t batch,
+                              uint32_t* d_status, size_t own_flags, hipStream_t s, MaskedSlice* sl) {
+  const size_t cnt = std::min(m.per, batch - b0), own_status = d_status ? 0 : kStatusBytes;
+  const size_t o_rows = align256(cnt * m.pay_len), o_plan = o_rows + align256(cnt * m.rows_len);
+  const size_t o_status = o_plan + align256(cnt * m.plan_len), o_flags = o_status + align256(cnt * own_status);
+  hipError_t e = restore_scratch(c, o_flags + align256(cnt * own_flags), s, &sl->scr);
+  if (e != hipSuccess) return e;
+  sl->cnt = cnt;
+  sl->rows = sl->scr + o_rows;
+  sl->plan = reinterpret_cast<uint32_t*>(sl->scr + o_plan);
+  sl->flags = sl->scr + o_flags;
+  sl->a = rec_args(p, d_shards + b0 * bstride, shard_len, bstride, d_present + b0 * p->n, cnt, sl->scr, m.pay_len,
+                   d_status ? d_status + 2 * b0 : reinterpret_cast<uint32_t*>(sl->scr + o_status));
+  return launch_reconstruct(c, sl->a, s);
+}
+
+// Orders the next use of the restore scratch behind this slice.
+hipError_t masked_done(np_ctx* c, hipStream_t s, hipError_t e) {
+  if (e != hipSuccess) return e;
+  c->restore_used = true;
+  return HIP(hipEventRecord(c->restore_done, s));
+}
+
 // np_restore_shards_batch_dev after validation: per slice of the batch, the
 // reconstruct into the payload scratch, then either the row-masked encode
 // straight into d_shards or the unchanged encode into scratch rows and the
 // copy of the absent ones.  Caller holds the context lock.
 hipError_t launch_restore(np_ctx* c, const np_code_params* p, uint8_t* d_shards, size_t shard_len, size_t bstride,
                           const uint8_t* d_present, size_t batch, uint32_t* d_status, hipStream_t s) {
-  const uint32_t n = static_cast<uint32_t>(p->n), k = static_cast<uint32_t>(p->k);
-  const uint32_t wanted_n = static_cast<uint32_t>(p->wanted_n);
-  const bool direct = np::masked_encode_supported(n, k);
-  const size_t pay_len = (shard_len / 2) * 2 * p->k;
-  const size_t rows_len = direct ? 0 : p->wanted_n * shard_len;  // scratch shard rows per payload
-  const size_t plan_len = direct ? np::restore_plan_words(n, k) * sizeof(uint32_t) : 0;
-  const size_t own_status = d_status ? 0 : kStatusBytes;
-  // The cap bounds the decoded payloads of a slice, and its scratch shard rows
-  // likewise (the plan and status come on top: bytes per payload).  Slices are
-  // multiples of 8 payloads where they can be: the fast kernels place a
-  // payload's tiles on one XCD only then (fast_common.hpp tile_of), and a slice
-  // of 1023 measured 1.5-1.7 x the reconstruct time of one of 1024.
-  size_t per = c->restore_cap / std::max(pay_len, rows_len);
-  per = per >= 8 ? per & ~size_t(7) : std::max<size_t>(1, per);
-  for (size_t b0 = 0; b0 < batch; b0 += per) {
-    const size_t cnt = std::min(per, batch - b0);
-    const size_t o_rows = align256(cnt * pay_len), o_plan = o_rows + align256(cnt * rows_len);
-    const size_t o_status = o_plan + align256(cnt * plan_len);
-    uint8_t* scr = nullptr;
-    hipError_t e = restore_scratch(c, o_status + align256(cnt * own_status), s, &scr);
-    if (e != hipSuccess) return e;
+  const MaskedShape m = masked_shape(c, p, shard_len);
+  for (size_t b0 = 0; b0 < batch; b0 += m.per) {
+    MaskedSlice sl;
+    hipError_t e = masked_reconstruct(c, p, m, d_shards, shard_len, bstride, d_present, b0, batch, d_status, 0, s, &sl);
     uint8_t* shards = d_shards + b0 * bstride;
-    np::ReconstructArgs a{};
-    a.shards = shards;
-    a.shard_len = shard_len;
-    a.batch_stride = bstride;
-    a.present = d_present + b0 * p->n;
-    a.locators = nullptr;  // computed on the device
-    a.batch = cnt;
-    a.n = n;
-    a.k = k;
-    a.out = scr;
-    a.out_stride = pay_len;
-    a.status = d_status ? d_status + 2 * b0 : reinterpret_cast<uint32_t*>(scr + o_status);
-    e = launch_reconstruct(c, a, s);
-    if (e == hipSuccess && wanted_n) {
-      if (direct) {
-        uint32_t* plan = reinterpret_cast<uint32_t*>(scr + o_plan);
-        e = HIP(np::launch_restore_plan(a.present, a.status, n, k, wanted_n, cnt, plan, s));
+    if (e == hipSuccess && m.wanted_n) {
+      if (m.direct) {
+        e = HIP(np::launch_restore_plan(sl.a.present, sl.a.status, m.n, m.k, m.wanted_n, sl.cnt, sl.plan, s));
         if (e == hipSuccess)
-          e = HIP(np::launch_encode_masked(c->T, enc_args(p, scr, pay_len, pay_len, cnt, shards, bstride), plan, s));
+          e = HIP(np::launch_encode_masked(c->T, enc_args(p, sl.scr, m.pay_len, m.pay_len, sl.cnt, shards, bstride),
+                                           sl.plan, s));
       } else {
-        uint8_t* rows = scr + o_rows;
-        e = launch_encode(c, enc_args(p, scr, pay_len, pay_len, cnt, rows, rows_len), s);
+        e = launch_encode(c, enc_args(p, sl.scr, m.pay_len, m.pay_len, sl.cnt, sl.rows, m.rows_len), s);
         if (e == hipSuccess)
-          e = HIP(np::launch_copy_absent_rows(rows, rows_len, shards, bstride, shard_len, a.present, a.status, n,
-                                              wanted_n, cnt, s));
+          e = HIP(np::launch_copy_absent_rows(sl.rows, m.rows_len, shards, bstride, shard_len, sl.a.present,
+                                              sl.a.status, m.n, m.wanted_n, sl.cnt, s));
       }
     }
-    if (e != hipSuccess) return e;
-    c->restore_used = true;
-    e = HIP(hipEventRecord(c->restore_done, s));
+    e = masked_done(c, s, e);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
@@ -1489,59 +1527,31 @@ hipError_t launch_restore(np_ctx* c, const np_code_params* p, uint8_t* d_shards,
 hipError_t launch_verify(np_ctx* c, const np_code_params* p, const uint8_t* d_shards, size_t shard_len,
                          size_t bstride, const uint8_t* d_present, size_t batch, uint32_t* d_bad_rows,
                          uint8_t* d_mismatch, uint32_t* d_status, hipStream_t s) {
-  const uint32_t n = static_cast<uint32_t>(p->n), k = static_cast<uint32_t>(p->k);
-  const uint32_t wanted_n = static_cast<uint32_t>(p->wanted_n);
-  const bool direct = np::masked_encode_supported(n, k);
-  const size_t pay_len = (shard_len / 2) * 2 * p->k;
-  const size_t rows_len = direct ? 0 : p->wanted_n * shard_len;  // scratch shard rows per payload
-  const size_t plan_len = direct ? np::restore_plan_words(n, k) * sizeof(uint32_t) : 0;
-  const size_t own_status = d_status ? 0 : kStatusBytes;
-  const size_t own_flags = d_mismatch ? 0 : p->n;
-  size_t per = c->restore_cap / std::max(pay_len, rows_len);  // as launch_restore
-  per = per >= 8 ? per & ~size_t(7) : std::max<size_t>(1, per);
-  for (size_t b0 = 0; b0 < batch; b0 += per) {
-    const size_t cnt = std::min(per, batch - b0);
-    const size_t o_rows = align256(cnt * pay_len), o_plan = o_rows + align256(cnt * rows_len);
-    const size_t o_status = o_plan + align256(cnt * plan_len), o_flags = o_status + align256(cnt * own_status);
-    uint8_t* scr = nullptr;
-    hipError_t e = restore_scratch(c, o_flags + align256(cnt * own_flags), s, &scr);
-    if (e != hipSuccess) return e;
+  const MaskedShape m = masked_shape(c, p, shard_len);
+  for (size_t b0 = 0; b0 < batch; b0 += m.per) {
+    MaskedSlice sl;
+    hipError_t e = masked_reconstruct(c, p, m, d_shards, shard_len, bstride, d_present, b0, batch, d_status,
+                                      d_mismatch ? 0 : p->n, s, &sl);
     const uint8_t* shards = d_shards + b0 * bstride;
-    uint8_t* flags = d_mismatch ? d_mismatch + b0 * p->n : scr + o_flags;
-    np::ReconstructArgs a{};
-    a.shards = shards;
-    a.shard_len = shard_len;
-    a.batch_stride = bstride;
-    a.present = d_present + b0 * p->n;
-    a.locators = nullptr;  // computed on the device
-    a.batch = cnt;
-    a.n = n;
-    a.k = k;
-    a.out = scr;
-    a.out_stride = pay_len;
-    a.status = d_status ? d_status + 2 * b0 : reinterpret_cast<uint32_t*>(scr + o_status);
-    e = launch_reconstruct(c, a, s);
-    if (e == hipSuccess) e = HIP(hipMemsetAsync(flags, 0, cnt * p->n, s));
-    if (e == hipSuccess && wanted_n > k) {
-      if (direct) {
-        uint32_t* plan = reinterpret_cast<uint32_t*>(scr + o_plan);
-        e = HIP(np::launch_verify_plan(a.present, a.status, n, k, wanted_n, cnt, plan, s));
+    uint8_t* flags = d_mismatch ? d_mismatch + b0 * p->n : sl.flags;
+    if (e == hipSuccess) e = HIP(hipMemsetAsync(flags, 0, sl.cnt * p->n, s));
+    if (e == hipSuccess && m.wanted_n > m.k) {
+      if (m.direct) {
+        e = HIP(np::launch_verify_plan(sl.a.present, sl.a.status, m.n, m.k, m.wanted_n, sl.cnt, sl.plan, s));
         // (EncodeArgs names the rows as the encode's output; the verify encode only reads them)
         if (e == hipSuccess)
           e = HIP(np::launch_encode_verify(
-              c->T, enc_args(p, scr, pay_len, pay_len, cnt, const_cast<uint8_t*>(shards), bstride), plan, flags, s));
+              c->T, enc_args(p, sl.scr, m.pay_len, m.pay_len, sl.cnt, const_cast<uint8_t*>(shards), bstride), sl.plan,
+              flags, s));
       } else {
-        uint8_t* rows = scr + o_rows;
-        e = launch_encode(c, enc_args(p, scr, pay_len, pay_len, cnt, rows, rows_len), s);
+        e = launch_encode(c, enc_args(p, sl.scr, m.pay_len, m.pay_len, sl.cnt, sl.rows, m.rows_len), s);
         if (e == hipSuccess)
-          e = HIP(np::launch_compare_present_rows(rows, rows_len, shards, bstride, shard_len, a.present, a.status, n,
-                                                  k, wanted_n, cnt, flags, s));
+          e = HIP(np::launch_compare_present_rows(sl.rows, m.rows_len, shards, bstride, shard_len, sl.a.present,
+                                                  sl.a.status, m.n, m.k, m.wanted_n, sl.cnt, flags, s));
       }
     }
-    if (e == hipSuccess) e = HIP(np::launch_verify_summary(flags, a.status, n, cnt, d_bad_rows + b0, s));
-    if (e != hipSuccess) return e;
-    c->restore_used = true;
-    e = HIP(hipEventRecord(c->restore_done, s));
+    if (e == hipSuccess) e = HIP(np::launch_verify_summary(flags, sl.a.status, m.n, sl.cnt, d_bad_rows + b0, s));
+    e = masked_done(c, s, e);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
@@ -1625,18 +1635,8 @@ int np_reconstruct_batch_dev(np_ctx* c, const np_code_params* p, const uint8_t* 
   std::memcpy(c->h_pres.p, present, batch * p->n);
   e = HIP(hipMemcpyAsync(c->d_present.p, c->h_pres.p, batch * p->n, hipMemcpyHostToDevice, s));
   if (e != hipSuccess) return dev_err(e);
-  np::ReconstructArgs a{};
-  a.shards = d_shards;
-  a.shard_len = shard_len;
-  a.batch_stride = bstride;
-  a.present = c->d_present.as<uint8_t>();
-  a.locators = nullptr;  // computed on the device
-  a.batch = batch;
-  a.n = static_cast<uint32_t>(p->n);
-  a.k = static_cast<uint32_t>(p->k);
-  a.out = d_out;
-  a.out_stride = out_stride;
-  e = HIP(launch_reconstruct(c, a, s));
+  e = HIP(launch_reconstruct(
+      c, rec_args(p, d_shards, shard_len, bstride, c->d_present.as<uint8_t>(), batch, d_out, out_stride, nullptr), s));
   if (e != hipSuccess) return dev_err(e);
   // the staged present mask is the context's: the call returns once the
   // stream is done with it
@@ -2291,9 +2291,7 @@ hipError_t ragged_masked_reconstruct(np_ctx* c, const np_code_params* p, const u
 hipError_t ragged_masked_done(np_ctx* c, hipStream_t s, hipError_t e) {
   e = big_done(c, s, e);
   e = ragged_done(c, s, e);
-  if (e != hipSuccess) return e;
-  c->restore_used = true;
-  return HIP(hipEventRecord(c->restore_done, s));
+  return masked_done(c, s, e);
 }
 
 // np_restore_shards_ragged_dev after validation.  Direct shapes, per slice: the

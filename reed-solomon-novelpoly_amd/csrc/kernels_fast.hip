@@ -131,60 +131,78 @@ __device__ __forceinline__ void shift_cq(const DevTables& T, const uint32_t* vp,
 // (level-4) butterfly group instead of after the whole high pass: encode
 // -1.9 % at config 3 (1.686 -> 1.655 ms, profiles/r04_ab.txt).
 
-// One workgroup: 256 chunks of one payload.  mod.rs:144-154 / inc_encode.rs:15-48.
-template <int K>
-__global__ __launch_bounds__(4 * K) __attribute__((amdgpu_waves_per_eu(4))) void k_encode_fast(DevTables T, EncodeArgs a, uint32_t nchunks, uint32_t tiles) {
-  using G = Geo<K>;
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  uint8_t* tile = smem;
-  uint32_t* VP = reinterpret_cast<uint32_t*>(smem + G::kTileBytes);  // 2 staged transforms
-#if NP_BOUNDS_CHECK
-  bounds_arm(bounds_of_enc(a));
-#endif
-  const TileRef tr = tile_of(blockIdx.x, tiles, (a.batch & 7u) == 0);
-  const uint32_t pb = tr.pb, tl = tr.tl;
-  const uint32_t ch0 = tl * kTile;
-  const uint32_t ncols = min(static_cast<uint32_t>(kTile), nchunks - ch0);
-  const uint8_t* pay = a.payloads + static_cast<size_t>(pb) * a.payload_stride;
-  uint8_t* out = a.shards + static_cast<size_t>(pb) * a.batch_stride + 2 * static_cast<size_t>(ch0);
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, g = uniform(tid >> 6);
-  const bool full =
-      ncols == kTile && rows_vec_ok(a.shards, a.batch_stride, a.shard_len);
+// The tile of a single-tile encode workgroup (workgroup-uniform).  The uniform
+// kernels fill it from the launch record and tile_of, the ragged ones from the
+// item's record (ragged_head); the flows below see nothing else of the caller.
+struct EncTile {
+  const uint8_t* pay;  // the payload and its length
+  size_t payload_len;
+  uint8_t* out;  // row 0 of the item at the tile's first column
+  size_t shard_len;
+  uint32_t ch0, ncols;  // first chunk, chunks of the tile
+  bool full, nt;        // whole tile of 8-byte row pieces; streaming row stores
+};
 
-  // ---- tile load: thread tid moves blocks (c0 + 16 i, m0), i = 0..15
-  {
-    const uint32_t c0 = tid / G::Q, m0 = tid % G::Q;
-    const uint32_t base = col_base<K>(c0) ^ (8u * m0);
-    const size_t gbase = static_cast<size_t>(ch0 + c0) * 2 * K + 8u * m0;
-    const bool fast = out_vec_ok(pay, 0) && static_cast<size_t>(ch0 + kTile) * 2 * K <= a.payload_len;
-    if (fast) {
-      uint2 v[16];
+__device__ __forceinline__ EncTile enc_tile(const EncodeArgs& a, uint32_t nchunks, TileRef tr) {
+  EncTile t;
+  t.pay = a.payloads + static_cast<size_t>(tr.pb) * a.payload_stride;
+  t.payload_len = a.payload_len;
+  t.ch0 = tr.tl * kTile;
+  t.ncols = min(static_cast<uint32_t>(kTile), nchunks - t.ch0);
+  t.out = a.shards + static_cast<size_t>(tr.pb) * a.batch_stride + 2 * static_cast<size_t>(t.ch0);
+  t.shard_len = a.shard_len;
+  t.full = t.ncols == kTile && rows_vec_ok(a.shards, a.batch_stride, a.shard_len);
+  t.nt = rows_nt(a.shards, a.batch_stride, a.shard_len);
+  return t;
+}
+
+// Tile load: thread tid moves blocks (c0 + 16 i, m0), i = 0..15; a tile that
+// reaches past the payload's end loads by bytes and pads with zeros.
+template <int K>
+__device__ __forceinline__ void load_tile(uint8_t* tile, const EncTile& t, uint32_t tid) {
+  using G = Geo<K>;
+  const uint32_t c0 = tid / G::Q, m0 = tid % G::Q;
+  const uint32_t base = col_base<K>(c0) ^ (8u * m0);
+  const size_t gbase = static_cast<size_t>(t.ch0 + c0) * 2 * K + 8u * m0;
+  const bool fast = out_vec_ok(t.pay, 0) && static_cast<size_t>(t.ch0 + kTile) * 2 * K <= t.payload_len;
+  if (fast) {
+    uint2 v[16];
 #pragma unroll
-      for (int i = 0; i < 16; ++i)
-        v[i] = (kExp & 4) ? make_uint2(i, tid) : load_once(pay + gbase + static_cast<size_t>(i) * 32 * K);
+    for (int i = 0; i < 16; ++i)
+      v[i] = (kExp & 4) ? make_uint2(i, tid) : load_once(t.pay + gbase + static_cast<size_t>(i) * 32 * K);
 #pragma unroll
-      for (int i = 0; i < 16; ++i) *reinterpret_cast<uint2*>(tile + (base ^ col_base_c<K>(16u * i))) = v[i];
-    } else {
+    for (int i = 0; i < 16; ++i) *reinterpret_cast<uint2*>(tile + (base ^ col_base_c<K>(16u * i))) = v[i];
+  } else {
 #pragma unroll 1
-      for (uint32_t i = 0; i < 16; ++i) {
-        const size_t g0 = gbase + static_cast<size_t>(i) * 32 * K;
-        uint32_t w[2] = {0, 0};
+    for (uint32_t i = 0; i < 16; ++i) {
+      const size_t g0 = gbase + static_cast<size_t>(i) * 32 * K;
+      uint32_t w[2] = {0, 0};
 #pragma unroll
-        for (int e = 0; e < 8; ++e)
-          if (g0 + e < a.payload_len) w[e >> 2] |= static_cast<uint32_t>(*NP_BCHK(pay + (g0 + e), 1, kBkPayloads)) << (8 * (e & 3));
-        *reinterpret_cast<uint2*>(tile + (base ^ col_base_c<K>(16u * i))) = make_uint2(w[0], w[1]);
-      }
+      for (int e = 0; e < 8; ++e)
+        if (g0 + e < t.payload_len) w[e >> 2] |= static_cast<uint32_t>(*NP_BCHK(t.pay + (g0 + e), 1, kBkPayloads)) << (8 * (e & 3));
+      *reinterpret_cast<uint2*>(tile + (base ^ col_base_c<K>(16u * i))) = make_uint2(w[0], w[1]);
     }
   }
-  const uint32_t nshift = a.n / K;
-  const bool nt = rows_nt(a.shards, a.batch_stride, a.shard_len);
-  const uint32_t wanted_store = ((kExp & 2) && a.k != 12345u) ? 0u : a.wanted_n;  // experiment: no stores
+}
+
+// One workgroup: 256 chunks of one payload, every row below wanted_n.
+// mod.rs:144-154 / inc_encode.rs:15-48.
+template <int K>
+__device__ __forceinline__ void encode_all(const DevTables& T, uint8_t* smem, uint32_t n, uint32_t wanted_n,
+                                           const EncTile& t) {
+  using G = Geo<K>;
+  uint8_t* tile = smem;
+  uint32_t* VP = reinterpret_cast<uint32_t*>(smem + G::kTileBytes);  // 2 staged transforms
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, g = uniform(tid >> 6);
+  load_tile<K>(tile, t, tid);
+  const uint32_t nshift = n / K;
+  const uint32_t wanted_store = ((kExp & 2) && n != 12345u) ? 0u : wanted_n;  // experiment: no stores
   // n <= 4K: the tables of every transform stay staged (one buffer each, as
   // k_encode_multi: no table load inside the shift loop, where it would wait
   // for the row stores issued before it); otherwise two buffers alternate
   const bool resident = nshift <= 4;
   if (resident) {
-    for (uint32_t sh = 0; sh < nshift && sh * K < a.wanted_n; ++sh)
+    for (uint32_t sh = 0; sh < nshift && sh * K < wanted_n; ++sh)
       stage_vpools<K, G::kThreads>(T, sh * K, VP + sh * G::kVPWords, true, enc_conv(K, sh));
   } else {
     stage_vpools<K, G::kThreads>(T, 0, VP, true);                                   // inverse transform, index 0
@@ -197,7 +215,7 @@ __global__ __launch_bounds__(4 * K) __attribute__((amdgpu_waves_per_eu(4))) void
   {
     uint32_t CL[16], CH[16];
     cq_read<K>(tile, cqb, CL, CH);
-    store_rows(out, a.shard_len, 16 * g, wanted_store, CL, CH, lane, ncols, full, nt);
+    store_rows(t.out, t.shard_len, 16 * g, wanted_store, CL, CH, lane, t.ncols, t.full, t.nt);
     tower_convert(T, CL, CH);  // transforms run in tower coordinates
     cq_levels<K, true, true, 0, false, kEncPrioCq>(T, VP, 0, g, CL, CH);
     // the quad items overlay payload blocks that other waves read: wait for
@@ -221,20 +239,29 @@ __global__ __launch_bounds__(4 * K) __attribute__((amdgpu_waves_per_eu(4))) void
     const uint32_t* vp = VP + (resident ? sh : (sh & 1u)) * G::kVPWords;
     shift_hi<K, SH>(T, vp, index, ML, MH, XL, XH, PL, PH);
     __syncthreads();  // the previous cq pass is done with the tile and with the other table buffer
-    if (!resident && sh + 1 < nshift && (sh + 1) * K < a.wanted_n)
+    if (!resident && sh + 1 < nshift && (sh + 1) * K < wanted_n)
       stage_vpools<K, G::kThreads>(T, (sh + 1) * K, VP + ((sh + 1) & 1u) * G::kVPWords, sh + 1 < 4,
                                    enc_conv(K, sh + 1));
     hi_write_q<K>(tile, g, lane, XL, XH);
     __syncthreads();
     cq_read_q(tile, g, lane, XL, XH);
     shift_cq<K, SH>(T, vp, index, g, XL, XH);
-    store_rows(out, a.shard_len, index + 16 * g, wanted_store, XL, XH, lane, ncols, full, nt);
+    store_rows(t.out, t.shard_len, index + 16 * g, wanted_store, XL, XH, lane, t.ncols, t.full, t.nt);
   };
-  if (nshift > 1 && K < a.wanted_n) shift(Int<1>{}, 1);
-  if (nshift > 2 && 2 * K < a.wanted_n) shift(Int<2>{}, 2);
-  if (nshift > 3 && 3 * K < a.wanted_n) shift(Int<3>{}, 3);
+  if (nshift > 1 && K < wanted_n) shift(Int<1>{}, 1);
+  if (nshift > 2 && 2 * K < wanted_n) shift(Int<2>{}, 2);
+  if (nshift > 3 && 3 * K < wanted_n) shift(Int<3>{}, 3);
 #pragma unroll 1
-  for (uint32_t sh = 4; sh < nshift && sh * K < a.wanted_n; ++sh) shift(Int<0>{}, sh);
+  for (uint32_t sh = 4; sh < nshift && sh * K < wanted_n; ++sh) shift(Int<0>{}, sh);
+}
+
+template <int K>
+__global__ __launch_bounds__(4 * K) __attribute__((amdgpu_waves_per_eu(4))) void k_encode_fast(DevTables T, EncodeArgs a, uint32_t nchunks, uint32_t tiles) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+#if NP_BOUNDS_CHECK
+  bounds_arm(bounds_of_enc(a));
+#endif
+  encode_all<K>(T, smem, a.n, a.wanted_n, enc_tile(a, nchunks, tile_of(blockIdx.x, tiles, (a.batch & 7u) == 0)));
 }
 
 // --------------------------------------------------------- masked encode ----
@@ -336,68 +363,44 @@ __device__ __forceinline__ void shift_cq_rows(const DevTables& T, const uint32_t
 // instance multiplies for itself (MODE 0).
 constexpr int kShift3Own = 30;
 
-template <int K>
-__global__ __launch_bounds__(4 * K) __attribute__((amdgpu_waves_per_eu(4))) void k_encode_masked(
-    DevTables T, EncodeArgs a, uint32_t nchunks, uint32_t tiles, const uint32_t* plan) {
+// What encode_planned does with the 16 rows of a wave and pass that its plan
+// marks: the restore stores them (here), the verify compares them with the
+// received rows (CompareRows, with compare_rows_masked).  kSeg0: whether the
+// plan can mark systematic rows.
+struct StoreRows {
+  static constexpr bool kSeg0 = true;
+  __device__ __forceinline__ void operator()(const EncTile& t, uint32_t row0, uint32_t mask, const uint32_t (&L)[16],
+                                             const uint32_t (&H)[16], uint32_t lane) const {
+    store_rows_masked(t.out, t.shard_len, row0, mask, L, H, lane, t.ncols, t.full, t.nt);
+  }
+};
+
+// The plan words of payload or item `i` (scalar loads).
+__device__ __forceinline__ cpool_t plan_of(const uint32_t* plan, size_t i, uint32_t n, uint32_t k) {
+  const uint32_t planw = static_cast<uint32_t>(restore_plan_words(n, k));
+  NP_BNOTE(plan + i * planw, 4u * planw, kBkRecords);
+  return (cpool_t)(plan) + i * planw;
+}
+
+// One workgroup: 256 chunks of one payload, the rows of its plan `seg` (segment
+// words, then row words) handed to `sink`.
+template <int K, typename SINK>
+__device__ __forceinline__ void encode_planned(const DevTables& T, uint8_t* smem, uint32_t n, const EncTile& t,
+                                               cpool_t seg, SINK sink) {
   using G = Geo<K>;
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   uint8_t* tile = smem;
   uint32_t* VP = reinterpret_cast<uint32_t*>(smem + G::kTileBytes);  // up to 4 staged transforms
-  const uint32_t nshift = a.n / K;
-  const uint32_t segw = static_cast<uint32_t>(restore_seg_words(a.n, K));
-  const uint32_t planw = static_cast<uint32_t>(restore_plan_words(a.n, K));
-#if NP_BOUNDS_CHECK
-  {
-    BoundsSet b = bounds_of_enc(a);
-    b.lo[kBkRecords] = reinterpret_cast<uint64_t>(plan);
-    b.hi[kBkRecords] = b.lo[kBkRecords] + a.batch * planw * 4u;
-    bounds_arm(b);
-  }
-#endif
-  const TileRef tr = tile_of(blockIdx.x, tiles, (a.batch & 7u) == 0);
-  const uint32_t pb = tr.pb, tl = tr.tl;
-  NP_BNOTE(plan + static_cast<size_t>(pb) * planw, 4u * planw, kBkRecords);
-  const cpool_t seg = (cpool_t)(plan) + static_cast<size_t>(pb) * planw;
-  const cpool_t rowbits = seg + segw;
-  const bool seg0 = (seg[0] & 1u) != 0;
+  const uint32_t nshift = n / K;
+  const cpool_t rowbits = seg + static_cast<uint32_t>(restore_seg_words(n, K));
+  const bool seg0 = SINK::kSeg0 && (seg[0] & 1u) != 0;
   const uint32_t first = next_segment(seg, 1, nshift);  // the first shift to run
-  if (!seg0 && first == nshift) return;                 // nothing to restore (or NeedMoreShards)
-  const uint32_t ch0 = tl * kTile;
-  const uint32_t ncols = min(static_cast<uint32_t>(kTile), nchunks - ch0);
-  const uint8_t* pay = a.payloads + static_cast<size_t>(pb) * a.payload_stride;
-  uint8_t* out = a.shards + static_cast<size_t>(pb) * a.batch_stride + 2 * static_cast<size_t>(ch0);
+  if (!seg0 && first == nshift) return;                 // no row of the plan (or NeedMoreShards)
   const uint32_t tid = threadIdx.x, lane = tid & 63u, g = uniform(tid >> 6);
-  const bool full = ncols == kTile && rows_vec_ok(a.shards, a.batch_stride, a.shard_len);
-
-  // ---- tile load (as k_encode_fast)
-  {
-    const uint32_t c0 = tid / G::Q, m0 = tid % G::Q;
-    const uint32_t base = col_base<K>(c0) ^ (8u * m0);
-    const size_t gbase = static_cast<size_t>(ch0 + c0) * 2 * K + 8u * m0;
-    const bool fast = out_vec_ok(pay, 0) && static_cast<size_t>(ch0 + kTile) * 2 * K <= a.payload_len;
-    if (fast) {
-      uint2 v[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) v[i] = load_once(pay + gbase + static_cast<size_t>(i) * 32 * K);
-#pragma unroll
-      for (int i = 0; i < 16; ++i) *reinterpret_cast<uint2*>(tile + (base ^ col_base_c<K>(16u * i))) = v[i];
-    } else {
-#pragma unroll 1
-      for (uint32_t i = 0; i < 16; ++i) {
-        const size_t g0 = gbase + static_cast<size_t>(i) * 32 * K;
-        uint32_t w[2] = {0, 0};
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          if (g0 + e < a.payload_len) w[e >> 2] |= static_cast<uint32_t>(*NP_BCHK(pay + (g0 + e), 1, kBkPayloads)) << (8 * (e & 3));
-        *reinterpret_cast<uint2*>(tile + (base ^ col_base_c<K>(16u * i))) = make_uint2(w[0], w[1]);
-      }
-    }
-  }
-  const bool nt = rows_nt(a.shards, a.batch_stride, a.shard_len);
+  load_tile<K>(tile, t, tid);
   // n <= 4K: one table buffer per transform that runs; otherwise two buffers
   // alternate, each shift staging the next one that runs
   const bool resident = nshift <= 4;
-  if (first < nshift) {
+  if (!SINK::kSeg0 || first < nshift) {
     stage_vpools<K, G::kThreads>(T, 0, VP, true);  // inverse transform, index 0
     if (resident) {
       for (uint32_t sh = first; sh < nshift; sh = next_segment(seg, sh + 1, nshift))
@@ -409,13 +412,15 @@ __global__ __launch_bounds__(4 * K) __attribute__((amdgpu_waves_per_eu(4))) void
   __syncthreads();
 
   const uint32_t cqb = col_base<K>(4 * lane) ^ (32u * g);  // blocks 4g..4g+3 of columns 4l..4l+3
-  // ---- cq pass: absent systematic rows, inverse levels 0..3
+  // ---- cq pass: marked systematic rows, inverse levels 0..3
   {
     uint32_t CL[16], CH[16];
     cq_read<K>(tile, cqb, CL, CH);
-    if (seg0) store_rows_masked(out, a.shard_len, 16 * g, restore_mask16(rowbits, 16 * g), CL, CH, lane, ncols, full, nt);
-    if (first == nshift) return;  // no parity row to restore
-    tower_convert(T, CL, CH);     // transforms run in tower coordinates
+    if constexpr (SINK::kSeg0) {
+      if (seg0) sink(t, 16 * g, restore_mask16(rowbits, 16 * g), CL, CH, lane);
+      if (first == nshift) return;  // no parity row of the plan
+    }
+    tower_convert(T, CL, CH);  // transforms run in tower coordinates
     cq_levels<K, true, true, 0, false, kEncPrioCq>(T, VP, 0, g, CL, CH);
     // the quad items overlay payload blocks that other waves read: wait for
     // every wave's cq_read
@@ -461,7 +466,7 @@ __global__ __launch_bounds__(4 * K) __attribute__((amdgpu_waves_per_eu(4))) void
     cq_read_q(tile, g, lane, XL, XH);
     const uint32_t mask = restore_mask16(rowbits, index + 16 * g);
     shift_cq_rows<K, SHC>(T, vp, index, g, XL, XH, mask);
-    store_rows_masked(out, a.shard_len, index + 16 * g, mask, XL, XH, lane, ncols, full, nt);
+    sink(t, index + 16 * g, mask, XL, XH, lane);
     slot ^= 1u;
   };
   const bool own3 = ((seg[0] >> 1) & 3u) != 3u;  // shift 1 or 2 skipped
@@ -491,6 +496,32 @@ __global__ __launch_bounds__(4 * K) __attribute__((amdgpu_waves_per_eu(4))) void
     shift(Int<0>{}, cur, nxt);
     cur = nxt;
   }
+}
+
+#if NP_BOUNDS_CHECK
+// bounds_of_enc plus the plan and (verify) the flag map.
+__device__ __forceinline__ BoundsSet bounds_of_enc_planned(const EncodeArgs& a, const uint32_t* plan,
+                                                           const uint8_t* flags) {
+  BoundsSet b = bounds_of_enc(a);  // (verify: shards are the received rows, read only)
+  b.lo[kBkRecords] = reinterpret_cast<uint64_t>(plan);
+  b.hi[kBkRecords] = b.lo[kBkRecords] + a.batch * restore_plan_words(a.n, a.k) * 4u;
+  if (flags) {
+    b.lo[kBkOut] = reinterpret_cast<uint64_t>(flags);
+    b.hi[kBkOut] = b.lo[kBkOut] + a.batch * static_cast<uint64_t>(a.n);
+  }
+  return b;
+}
+#endif
+
+template <int K>
+__global__ __launch_bounds__(4 * K) __attribute__((amdgpu_waves_per_eu(4))) void k_encode_masked(
+    DevTables T, EncodeArgs a, uint32_t nchunks, uint32_t tiles, const uint32_t* plan) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+#if NP_BOUNDS_CHECK
+  bounds_arm(bounds_of_enc_planned(a, plan, nullptr));
+#endif
+  const TileRef tr = tile_of(blockIdx.x, tiles, (a.batch & 7u) == 0);
+  encode_planned<K>(T, smem, a.n, enc_tile(a, nchunks, tr), plan_of(plan, tr.pb, a.n, K), StoreRows{});
 }
 
 // ----------------------------------------------------- multi-tile encode ----
@@ -1671,25 +1702,40 @@ uint32_t tiles_per_workgroup(size_t batch, uint32_t tiles, const char* knob) {
   return static_cast<uint32_t>(std::max<size_t>(1, std::min<size_t>(tiles, want)));
 }
 
-template <int K>
-hipError_t launch_encode_k(const DevTables& T, const EncodeArgs& a, hipStream_t s) {
+// The grid of an encode launch: the chunks of a payload, their 256-chunk tiles
+// and the workgroups of tpw_of(tiles) tiles each, range-checked;
+// launch(nchunks, tiles, tpw, blocks) starts the kernel.
+template <typename TPW, typename F>
+hipError_t with_encode_grid(const EncodeArgs& a, TPW tpw_of, F launch) {
   const size_t nchunks = (a.payload_len + 2 * a.k - 1) / (2 * a.k);
   if (nchunks == 0 || a.batch == 0) return hipSuccess;
   if (nchunks > 0xffffffffu) return hipErrorInvalidValue;
   const uint32_t tiles = static_cast<uint32_t>((nchunks + kTile - 1) / kTile);
-  const uint32_t tpw = a.n <= kEncBuffers * K ? tiles_per_workgroup<K>(a.batch, tiles, "NP_ENC_TPW") : 1u;
+  const uint32_t tpw = tpw_of(tiles);
   const size_t blocks = a.batch * ((tiles + tpw - 1) / tpw);
   if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
-  if constexpr (kMultiTile<K>) {
-    if (a.n <= kEncBuffers * K) {
-      k_encode_multi<K><<<static_cast<uint32_t>(blocks), Geo<K>::kThreads, encode_multi_lds_bytes<K>(), s>>>(
-          EncLaunch{T, a, static_cast<uint32_t>(nchunks), tiles, tpw});
-      return hipGetLastError();
-    }
-  }
-  k_encode_fast<K><<<static_cast<uint32_t>(blocks), Geo<K>::kThreads, encode_lds_bytes<K>(), s>>>(
-      T, a, static_cast<uint32_t>(nchunks), tiles);
+  launch(static_cast<uint32_t>(nchunks), tiles, tpw, static_cast<uint32_t>(blocks));
   return hipGetLastError();
+}
+// One tile per workgroup at every K (the masked and verify encodes: the
+// multi-tile encode counts its outstanding row stores, which they do not issue).
+uint32_t one_tile(uint32_t) { return 1u; }
+
+template <int K>
+hipError_t launch_encode_k(const DevTables& T, const EncodeArgs& a, hipStream_t s) {
+  const bool multi = kMultiTile<K> && a.n <= kEncBuffers * K;
+  return with_encode_grid(
+      a, [&](uint32_t tiles) { return multi ? tiles_per_workgroup<K>(a.batch, tiles, "NP_ENC_TPW") : 1u; },
+      [&](uint32_t nchunks, uint32_t tiles, uint32_t tpw, uint32_t blocks) {
+        if constexpr (kMultiTile<K>) {
+          if (multi) {
+            k_encode_multi<K><<<blocks, Geo<K>::kThreads, encode_multi_lds_bytes<K>(), s>>>(
+                EncLaunch{T, a, nchunks, tiles, tpw});
+            return;
+          }
+        }
+        k_encode_fast<K><<<blocks, Geo<K>::kThreads, encode_lds_bytes<K>(), s>>>(T, a, nchunks, tiles);
+      });
 }
 
 template <int K, int NQ>
@@ -1789,78 +1835,16 @@ hipError_t launch_reconstruct_fast(const DevTables& T, const ReconstructArgs& a,
   }
 }
 
-namespace {
-hipError_t configure_masked_kernels();  // below, with the masked encode's launchers
-hipError_t configure_verify_kernels();  // with the verify encode
-hipError_t configure_ragged_kernels();  // at the end of the file, with the ragged kernels
-hipError_t configure_ragged_masked_kernels();  // behind them, with the ragged restore and verify
-}
-
-hipError_t configure_fast_kernels() {
-  hipError_t e = hipSuccess;
-  auto set = [&](const void* f, size_t bytes) {
-    hipError_t r = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
-    if (r != hipSuccess && e == hipSuccess) e = r;
-  };
-  set(reinterpret_cast<const void*>(&k_encode_fast<64>), encode_lds_bytes<64>());
-  set(reinterpret_cast<const void*>(&k_encode_fast<128>), encode_lds_bytes<128>());
-  set(reinterpret_cast<const void*>(&k_encode_fast<256>), encode_lds_bytes<256>());
-  set(reinterpret_cast<const void*>(&k_encode_multi<256>), encode_multi_lds_bytes<256>());
-  set(reinterpret_cast<const void*>(&k_reconstruct_fast<64, 2, 2>), reconstruct_lds_bytes<64, 2>());
-  set(reinterpret_cast<const void*>(&k_reconstruct_fast<64, 4, 2>), reconstruct_lds_bytes<64, 4>());
-  set(reinterpret_cast<const void*>(&k_reconstruct_fast<64, 4, 4>), reconstruct_lds_bytes<64, 4>());
-  set(reinterpret_cast<const void*>(&k_reconstruct_fast<128, 2, 2>), reconstruct_lds_bytes<128, 2>());
-  set(reinterpret_cast<const void*>(&k_reconstruct_fast<128, 4, 2>), reconstruct_lds_bytes<128, 4>());
-  set(reinterpret_cast<const void*>(&k_reconstruct_fast<128, 4, 4>), reconstruct_lds_bytes<128, 4>());
-  set(reinterpret_cast<const void*>(&k_reconstruct_fast<256, 2, 2>), reconstruct_lds_bytes<256, 2>());
-  set(reinterpret_cast<const void*>(&k_reconstruct_fast<256, 4, 2>), reconstruct_lds_bytes<256, 4>());
-  set(reinterpret_cast<const void*>(&k_reconstruct_fast<256, 4, 4>), reconstruct_lds_bytes<256, 4>());
-  set(reinterpret_cast<const void*>(&k_reconstruct_fast<64, 8, 2>), reconstruct_lds_bytes<64, 8>());
-  set(reinterpret_cast<const void*>(&k_reconstruct_fast<64, 8, 8>), reconstruct_lds_bytes<64, 8>());
-  set(reinterpret_cast<const void*>(&k_reconstruct_fast<128, 8, 2>), reconstruct_lds_bytes<128, 8>());
-  set(reinterpret_cast<const void*>(&k_reconstruct_fast<128, 8, 8>), reconstruct_lds_bytes<128, 8>());
-  set(reinterpret_cast<const void*>(&k_reconstruct_fast<256, 8, 2>), reconstruct_lds_bytes<256, 8>());
-  set(reinterpret_cast<const void*>(&k_reconstruct_fast<256, 8, 8>), reconstruct_lds_bytes<256, 8>());
-  if (e == hipSuccess) e = configure_masked_kernels();
-  if (e == hipSuccess) e = configure_verify_kernels();
-  if (e == hipSuccess) e = configure_ragged_kernels();
-  if (e == hipSuccess) e = configure_ragged_masked_kernels();
-  return e;
-}
-
 hipError_t bounds_take_fast(uint32_t out[8]) { return bounds_take_tu(out); }
 
 // ------------------------------------------- masked encode: launchers ----
-// The last references in this file, so that k_encode_masked's instances come
-// after every older kernel in the code object (the older kernels' assembly,
-// block labels included, stays what it was: tools/isa_funcdiff.py).
 namespace {
 
-// One tile per workgroup at every K: the multi-tile encode counts its
-// outstanding row stores, which a masked pass does not issue.
 template <int K>
 hipError_t launch_encode_masked_k(const DevTables& T, const EncodeArgs& a, const uint32_t* plan, hipStream_t s) {
-  const size_t nchunks = (a.payload_len + 2 * a.k - 1) / (2 * a.k);
-  if (nchunks == 0 || a.batch == 0) return hipSuccess;
-  if (nchunks > 0xffffffffu) return hipErrorInvalidValue;
-  const uint32_t tiles = static_cast<uint32_t>((nchunks + kTile - 1) / kTile);
-  const size_t blocks = a.batch * tiles;
-  if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
-  k_encode_masked<K><<<static_cast<uint32_t>(blocks), Geo<K>::kThreads, encode_lds_bytes<K>(), s>>>(
-      T, a, static_cast<uint32_t>(nchunks), tiles, plan);
-  return hipGetLastError();
-}
-
-hipError_t configure_masked_kernels() {
-  hipError_t e = hipSuccess;
-  auto set = [&](const void* f, size_t bytes) {
-    hipError_t r = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
-    if (r != hipSuccess && e == hipSuccess) e = r;
-  };
-  set(reinterpret_cast<const void*>(&k_encode_masked<64>), encode_lds_bytes<64>());
-  set(reinterpret_cast<const void*>(&k_encode_masked<128>), encode_lds_bytes<128>());
-  set(reinterpret_cast<const void*>(&k_encode_masked<256>), encode_lds_bytes<256>());
-  return e;
+  return with_encode_grid(a, one_tile, [&](uint32_t nchunks, uint32_t tiles, uint32_t, uint32_t blocks) {
+    k_encode_masked<K><<<blocks, Geo<K>::kThreads, encode_lds_bytes<K>(), s>>>(T, a, nchunks, tiles, plan);
+  });
 }
 
 }  // namespace
@@ -1888,7 +1872,6 @@ hipError_t launch_encode_masked(const DevTables& T, const EncodeArgs& a, const u
 // equals its re-encoding), so a payload with no marked row exits before the
 // tile load; the skipped shifts, the unstaged tables, the `rows` mask of the cq
 // levels and kShift3Own are the masked encode's.
-// The last kernel of this file: every older kernel's assembly stays what it was.
 namespace {
 
 // Received rows a wave loads before it compares them.  A workgroup's waves
@@ -1963,184 +1946,35 @@ __device__ __forceinline__ void compare_rows_masked(const uint8_t* in, size_t sh
   }
 }
 
+// encode_planned's sink of the verify: the tile's shard rows are the received
+// ones, `flag` the flag row of the payload.  The verify plan never marks segment 0.
+struct CompareRows {
+  static constexpr bool kSeg0 = false;
+  uint8_t* flag;
+  __device__ __forceinline__ void operator()(const EncTile& t, uint32_t row0, uint32_t mask, const uint32_t (&L)[16],
+                                             const uint32_t (&H)[16], uint32_t lane) const {
+    compare_rows_masked(t.out, t.shard_len, row0, mask, L, H, lane, t.ncols, t.full, flag);
+  }
+};
+
 template <int K>
 __global__ __launch_bounds__(4 * K) __attribute__((amdgpu_waves_per_eu(4))) void k_encode_verify(
     DevTables T, EncodeArgs a, uint32_t nchunks, uint32_t tiles, const uint32_t* plan, uint8_t* flags) {
-  using G = Geo<K>;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  uint8_t* tile = smem;
-  uint32_t* VP = reinterpret_cast<uint32_t*>(smem + G::kTileBytes);  // up to 4 staged transforms
-  const uint32_t nshift = a.n / K;
-  const uint32_t segw = static_cast<uint32_t>(restore_seg_words(a.n, K));
-  const uint32_t planw = static_cast<uint32_t>(restore_plan_words(a.n, K));
 #if NP_BOUNDS_CHECK
-  {
-    BoundsSet b = bounds_of_enc(a);  // shards: the received rows, read only
-    b.lo[kBkRecords] = reinterpret_cast<uint64_t>(plan);
-    b.hi[kBkRecords] = b.lo[kBkRecords] + a.batch * planw * 4u;
-    b.lo[kBkOut] = reinterpret_cast<uint64_t>(flags);
-    b.hi[kBkOut] = b.lo[kBkOut] + a.batch * static_cast<uint64_t>(a.n);
-    bounds_arm(b);
-  }
+  bounds_arm(bounds_of_enc_planned(a, plan, flags));
 #endif
   const TileRef tr = tile_of(blockIdx.x, tiles, (a.batch & 7u) == 0);
-  const uint32_t pb = tr.pb, tl = tr.tl;
-  NP_BNOTE(plan + static_cast<size_t>(pb) * planw, 4u * planw, kBkRecords);
-  const cpool_t seg = (cpool_t)(plan) + static_cast<size_t>(pb) * planw;
-  const cpool_t rowbits = seg + segw;
-  const uint32_t first = next_segment(seg, 1, nshift);  // the first shift to run
-  if (first == nshift) return;                          // no row to compare (or NeedMoreShards)
-  const uint32_t ch0 = tl * kTile;
-  const uint32_t ncols = min(static_cast<uint32_t>(kTile), nchunks - ch0);
-  const uint8_t* pay = a.payloads + static_cast<size_t>(pb) * a.payload_stride;
-  const uint8_t* in = a.shards + static_cast<size_t>(pb) * a.batch_stride + 2 * static_cast<size_t>(ch0);
-  uint8_t* flag = flags + static_cast<size_t>(pb) * a.n;
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, g = uniform(tid >> 6);
-  const bool full = ncols == kTile && rows_vec_ok(a.shards, a.batch_stride, a.shard_len);
-
-  // ---- tile load (as k_encode_fast)
-  {
-    const uint32_t c0 = tid / G::Q, m0 = tid % G::Q;
-    const uint32_t base = col_base<K>(c0) ^ (8u * m0);
-    const size_t gbase = static_cast<size_t>(ch0 + c0) * 2 * K + 8u * m0;
-    const bool fast = out_vec_ok(pay, 0) && static_cast<size_t>(ch0 + kTile) * 2 * K <= a.payload_len;
-    if (fast) {
-      uint2 v[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) v[i] = load_once(pay + gbase + static_cast<size_t>(i) * 32 * K);
-#pragma unroll
-      for (int i = 0; i < 16; ++i) *reinterpret_cast<uint2*>(tile + (base ^ col_base_c<K>(16u * i))) = v[i];
-    } else {
-#pragma unroll 1
-      for (uint32_t i = 0; i < 16; ++i) {
-        const size_t g0 = gbase + static_cast<size_t>(i) * 32 * K;
-        uint32_t w[2] = {0, 0};
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          if (g0 + e < a.payload_len) w[e >> 2] |= static_cast<uint32_t>(*NP_BCHK(pay + (g0 + e), 1, kBkPayloads)) << (8 * (e & 3));
-        *reinterpret_cast<uint2*>(tile + (base ^ col_base_c<K>(16u * i))) = make_uint2(w[0], w[1]);
-      }
-    }
-  }
-  // n <= 4K: one table buffer per transform that runs; otherwise two buffers
-  // alternate, each shift staging the next one that runs
-  const bool resident = nshift <= 4;
-  stage_vpools<K, G::kThreads>(T, 0, VP, true);  // inverse transform, index 0
-  if (resident) {
-    for (uint32_t sh = first; sh < nshift; sh = next_segment(seg, sh + 1, nshift))
-      stage_vpools<K, G::kThreads>(T, sh * K, VP + sh * G::kVPWords, true, enc_conv_u<K>(sh));
-  } else {
-    stage_vpools<K, G::kThreads>(T, first * K, VP + G::kVPWords, uniform_b(first < 4), enc_conv_u<K>(first));
-  }
-  __syncthreads();
-
-  const uint32_t cqb = col_base<K>(4 * lane) ^ (32u * g);  // blocks 4g..4g+3 of columns 4l..4l+3
-  // ---- cq pass: inverse levels 0..3
-  {
-    uint32_t CL[16], CH[16];
-    cq_read<K>(tile, cqb, CL, CH);
-    tower_convert(T, CL, CH);  // transforms run in tower coordinates
-    cq_levels<K, true, true, 0, false, kEncPrioCq>(T, VP, 0, g, CL, CH);
-    // the quad items overlay payload blocks that other waves read: wait for
-    // every wave's cq_read
-    __syncthreads();
-    cq_write_q(tile, g, lane, CL, CH);
-  }
-  __syncthreads();
-  // ---- high layout: inverse levels 4.. -> coefficients M
-  uint32_t ML[16], MH[16];
-  hi_read_q<K>(tile, g, lane, ML, MH);
-  hi_levels<K, true, true, 0, 0, kEncPrio>(T, VP, 0, ML, MH);
-#pragma unroll
-  for (int q = 0; q < 16; ++q) asm volatile("" : "+v"(ML[q]), "+v"(MH[q]));  // materialise M once
-
-  // top-level products of shift 1, then of shifts 1 ^ 2 (fwd_top); zero, so that
-  // a shift 2 without shift 1 accumulates into defined values (which nobody reads)
-  uint32_t PL[8] = {}, PH[8] = {};
-  uint32_t slot = 1;  // !resident: the table buffer of the shift that runs
-  // shift sh; nxt: the next shift that runs (nshift: none)
-  auto shift = [&](auto shc, uint32_t sh, uint32_t nxt) __attribute__((always_inline)) {
-    constexpr int SH = decltype(shc)::value;
-    constexpr int SHC = SH == kShift3Own ? 3 : SH;
-    const uint32_t index = sh * K;
-    uint32_t XL[16], XH[16];
-    const uint32_t* vp = VP + (resident ? sh : slot) * G::kVPWords;
-    if constexpr (SH == kShift3Own) {
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        XL[q] = ML[q];
-        XH[q] = MH[q];
-      }
-      fwd_top<K, 0, 0>(T, vp, index, XL, XH, PL, PH);
-      hi_levels<K, false, false, 1, 0, kEncPrio>(T, vp, index, XL, XH);
-    } else {
-      shift_hi<K, SH>(T, vp, index, ML, MH, XL, XH, PL, PH);
-    }
-    __syncthreads();  // the previous cq pass is done with the tile and with the other table buffer
-    if (!resident && nxt < nshift)
-      stage_vpools<K, G::kThreads>(T, nxt * K, VP + (slot ^ 1u) * G::kVPWords, uniform_b(nxt < 4),
-                                   enc_conv_u<K>(nxt));
-    hi_write_q<K>(tile, g, lane, XL, XH);
-    __syncthreads();
-    cq_read_q(tile, g, lane, XL, XH);
-    const uint32_t mask = restore_mask16(rowbits, index + 16 * g);
-    shift_cq_rows<K, SHC>(T, vp, index, g, XL, XH, mask);
-    compare_rows_masked(in, a.shard_len, index + 16 * g, mask, XL, XH, lane, ncols, full, flag);
-    slot ^= 1u;
-  };
-  const bool own3 = ((seg[0] >> 1) & 3u) != 3u;  // shift 1 or 2 skipped
-  // cur: the next shift to run; nshift (2 at n = 2K: not "shift 2") when none is left
-  uint32_t cur = first;
-  if (cur == 1) {
-    const uint32_t nxt = next_segment(seg, 2, nshift);
-    shift(Int<1>{}, 1, nxt);
-    cur = nxt;
-  }
-  if (cur == 2 && cur < nshift) {
-    const uint32_t nxt = next_segment(seg, 3, nshift);
-    shift(Int<2>{}, 2, nxt);
-    cur = nxt;
-  }
-  if (cur == 3 && cur < nshift) {
-    const uint32_t nxt = next_segment(seg, 4, nshift);
-    if (own3)
-      shift(Int<kShift3Own>{}, 3, nxt);
-    else
-      shift(Int<3>{}, 3, nxt);
-    cur = nxt;
-  }
-#pragma unroll 1
-  while (cur < nshift) {
-    const uint32_t nxt = next_segment(seg, cur + 1, nshift);
-    shift(Int<0>{}, cur, nxt);
-    cur = nxt;
-  }
+  encode_planned<K>(T, smem, a.n, enc_tile(a, nchunks, tr), plan_of(plan, tr.pb, a.n, K),
+                    CompareRows{flags + static_cast<size_t>(tr.pb) * a.n});
 }
 
 template <int K>
 hipError_t launch_encode_verify_k(const DevTables& T, const EncodeArgs& a, const uint32_t* plan, uint8_t* flags,
                                   hipStream_t s) {
-  const size_t nchunks = (a.payload_len + 2 * a.k - 1) / (2 * a.k);
-  if (nchunks == 0 || a.batch == 0) return hipSuccess;
-  if (nchunks > 0xffffffffu) return hipErrorInvalidValue;
-  const uint32_t tiles = static_cast<uint32_t>((nchunks + kTile - 1) / kTile);
-  const size_t blocks = a.batch * tiles;
-  if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
-  k_encode_verify<K><<<static_cast<uint32_t>(blocks), Geo<K>::kThreads, encode_lds_bytes<K>(), s>>>(
-      T, a, static_cast<uint32_t>(nchunks), tiles, plan, flags);
-  return hipGetLastError();
-}
-
-hipError_t configure_verify_kernels() {
-  hipError_t e = hipSuccess;
-  auto set = [&](const void* f, size_t bytes) {
-    hipError_t r = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
-    if (r != hipSuccess && e == hipSuccess) e = r;
-  };
-  set(reinterpret_cast<const void*>(&k_encode_verify<64>), encode_lds_bytes<64>());
-  set(reinterpret_cast<const void*>(&k_encode_verify<128>), encode_lds_bytes<128>());
-  set(reinterpret_cast<const void*>(&k_encode_verify<256>), encode_lds_bytes<256>());
-  return e;
+  return with_encode_grid(a, one_tile, [&](uint32_t nchunks, uint32_t tiles, uint32_t, uint32_t blocks) {
+    k_encode_verify<K><<<blocks, Geo<K>::kThreads, encode_lds_bytes<K>(), s>>>(T, a, nchunks, tiles, plan, flags);
+  });
 }
 
 }  // namespace
@@ -2166,7 +2000,6 @@ hipError_t launch_encode_verify(const DevTables& T, const EncodeArgs& a, const u
 // the table (kRaggedNoItem) exit, workgroup-uniformly, before any barrier of
 // the flow.  The present flags, the prefix records and the status stay per
 // item at their fixed strides.
-// Behind every older kernel of this file: their assembly stays what it was.
 namespace {
 
 typedef const __attribute__((address_space(4))) uint64_t* crec_t;
@@ -2213,109 +2046,32 @@ __device__ __forceinline__ BoundsSet bounds_of_ragged(const RaggedArgs& r, const
 }
 #endif
 
+// The item's tile: what enc_tile derives per launch, per item.
+__device__ __forceinline__ EncTile enc_tile(const RaggedHead& h) {
+  EncTile t;
+  t.pay = reinterpret_cast<const uint8_t*>(h.data);
+  t.payload_len = h.data_len;
+  t.shard_len = h.shard_len;
+  uint8_t* const shards = reinterpret_cast<uint8_t*>(h.shards);
+  const uint32_t nchunks = static_cast<uint32_t>(t.shard_len / 2);  // = ceil(payload_len / 2K), validated by the host
+  t.ch0 = h.tile * kTile;
+  t.ncols = min(static_cast<uint32_t>(kTile), nchunks - t.ch0);
+  t.out = shards + 2 * static_cast<size_t>(t.ch0);
+  t.full = t.ncols == kTile && rows_vec_ok(shards, 0, t.shard_len);
+  t.nt = rows_nt(shards, 0, t.shard_len);
+  return t;
+}
+
 // One workgroup: 256 chunks of one item (k_encode_fast's flow).
 template <int K>
 __global__ __launch_bounds__(4 * K) __attribute__((amdgpu_waves_per_eu(4))) void k_encode_ragged(DevTables T, RaggedArgs r) {
-  using G = Geo<K>;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  uint8_t* tile = smem;
-  uint32_t* VP = reinterpret_cast<uint32_t*>(smem + G::kTileBytes);  // 2 staged transforms
 #if NP_BOUNDS_CHECK
   bounds_arm(bounds_of_ragged(r, T, false));
 #endif
   const RaggedHead h = ragged_head(r);
   if (h.item == kRaggedNoItem) return;  // padding of the plan
-  const uint8_t* pay = reinterpret_cast<const uint8_t*>(h.data);
-  const size_t payload_len = h.data_len, shard_len = h.shard_len;
-  uint8_t* const shards = reinterpret_cast<uint8_t*>(h.shards);
-  const uint32_t nchunks = static_cast<uint32_t>(shard_len / 2);  // = ceil(payload_len / 2K), validated by the host
-  const uint32_t ch0 = h.tile * kTile;
-  const uint32_t ncols = min(static_cast<uint32_t>(kTile), nchunks - ch0);
-  uint8_t* out = shards + 2 * static_cast<size_t>(ch0);
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, g = uniform(tid >> 6);
-  const bool full = ncols == kTile && rows_vec_ok(shards, 0, shard_len);
-
-  // ---- tile load: thread tid moves blocks (c0 + 16 i, m0), i = 0..15
-  {
-    const uint32_t c0 = tid / G::Q, m0 = tid % G::Q;
-    const uint32_t base = col_base<K>(c0) ^ (8u * m0);
-    const size_t gbase = static_cast<size_t>(ch0 + c0) * 2 * K + 8u * m0;
-    const bool fast = out_vec_ok(pay, 0) && static_cast<size_t>(ch0 + kTile) * 2 * K <= payload_len;
-    if (fast) {
-      uint2 v[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) v[i] = load_once(pay + gbase + static_cast<size_t>(i) * 32 * K);
-#pragma unroll
-      for (int i = 0; i < 16; ++i) *reinterpret_cast<uint2*>(tile + (base ^ col_base_c<K>(16u * i))) = v[i];
-    } else {
-#pragma unroll 1
-      for (uint32_t i = 0; i < 16; ++i) {
-        const size_t g0 = gbase + static_cast<size_t>(i) * 32 * K;
-        uint32_t w[2] = {0, 0};
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          if (g0 + e < payload_len) w[e >> 2] |= static_cast<uint32_t>(*NP_BCHK(pay + (g0 + e), 1, kBkPayloads)) << (8 * (e & 3));
-        *reinterpret_cast<uint2*>(tile + (base ^ col_base_c<K>(16u * i))) = make_uint2(w[0], w[1]);
-      }
-    }
-  }
-  const uint32_t nshift = r.n / K;
-  const uint32_t wanted_n = r.wanted_n;
-  const bool nt = rows_nt(shards, 0, shard_len);
-  // n <= 4K: the tables of every transform stay staged; otherwise two buffers alternate
-  const bool resident = nshift <= 4;
-  if (resident) {
-    for (uint32_t sh = 0; sh < nshift && sh * K < wanted_n; ++sh)
-      stage_vpools<K, G::kThreads>(T, sh * K, VP + sh * G::kVPWords, true, enc_conv(K, sh));
-  } else {
-    stage_vpools<K, G::kThreads>(T, 0, VP, true);                                   // inverse transform, index 0
-    if (nshift > 1) stage_vpools<K, G::kThreads>(T, K, VP + G::kVPWords, true, enc_conv(K, 1));  // first shift
-  }
-  __syncthreads();
-
-  const uint32_t cqb = col_base<K>(4 * lane) ^ (32u * g);  // blocks 4g..4g+3 of columns 4l..4l+3
-  // ---- cq pass: systematic rows, inverse levels 0..3
-  {
-    uint32_t CL[16], CH[16];
-    cq_read<K>(tile, cqb, CL, CH);
-    store_rows(out, shard_len, 16 * g, wanted_n, CL, CH, lane, ncols, full, nt);
-    tower_convert(T, CL, CH);  // transforms run in tower coordinates
-    cq_levels<K, true, true, 0, false, kEncPrioCq>(T, VP, 0, g, CL, CH);
-    // the quad items overlay payload blocks that other waves read: wait for
-    // every wave's cq_read
-    __syncthreads();
-    cq_write_q(tile, g, lane, CL, CH);
-  }
-  __syncthreads();
-  // ---- high layout: inverse levels 4.. -> coefficients M
-  uint32_t ML[16], MH[16];
-  hi_read_q<K>(tile, g, lane, ML, MH);
-  hi_levels<K, true, true, 0, 0, kEncPrio>(T, VP, 0, ML, MH);
-#pragma unroll
-  for (int q = 0; q < 16; ++q) asm volatile("" : "+v"(ML[q]), "+v"(MH[q]));  // materialise M once
-
-  uint32_t PL[8], PH[8];  // top-level products of shift 1, then of shifts 1 ^ 2 (fwd_top)
-  auto shift = [&](auto shc, uint32_t sh) __attribute__((always_inline)) {
-    constexpr int SH = decltype(shc)::value;
-    const uint32_t index = sh * K;
-    uint32_t XL[16], XH[16];
-    const uint32_t* vp = VP + (resident ? sh : (sh & 1u)) * G::kVPWords;
-    shift_hi<K, SH>(T, vp, index, ML, MH, XL, XH, PL, PH);
-    __syncthreads();  // the previous cq pass is done with the tile and with the other table buffer
-    if (!resident && sh + 1 < nshift && (sh + 1) * K < wanted_n)
-      stage_vpools<K, G::kThreads>(T, (sh + 1) * K, VP + ((sh + 1) & 1u) * G::kVPWords, sh + 1 < 4,
-                                   enc_conv(K, sh + 1));
-    hi_write_q<K>(tile, g, lane, XL, XH);
-    __syncthreads();
-    cq_read_q(tile, g, lane, XL, XH);
-    shift_cq<K, SH>(T, vp, index, g, XL, XH);
-    store_rows(out, shard_len, index + 16 * g, wanted_n, XL, XH, lane, ncols, full, nt);
-  };
-  if (nshift > 1 && K < wanted_n) shift(Int<1>{}, 1);
-  if (nshift > 2 && 2 * K < wanted_n) shift(Int<2>{}, 2);
-  if (nshift > 3 && 3 * K < wanted_n) shift(Int<3>{}, 3);
-#pragma unroll 1
-  for (uint32_t sh = 4; sh < nshift && sh * K < wanted_n; ++sh) shift(Int<0>{}, sh);
+  encode_all<K>(T, smem, r.n, r.wanted_n, enc_tile(h));
 }
 
 // One workgroup: one 256-column tile of one item, decoded as k_reconstruct_fast
@@ -2388,28 +2144,6 @@ hipError_t launch_reconstruct_ragged_nq(const DevTables& T, const RaggedArgs& r,
   return launch_reconstruct_ragged_k<K, 2>(T, r, s);
 }
 
-template <int K>
-void configure_ragged_k(hipError_t& e) {
-  auto set = [&](const void* f, size_t bytes) {
-    hipError_t x = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
-    if (x != hipSuccess && e == hipSuccess) e = x;
-  };
-  set(reinterpret_cast<const void*>(&k_encode_ragged<K>), encode_lds_bytes<K>());
-  set(reinterpret_cast<const void*>(&k_reconstruct_ragged<K, 2, 2>), reconstruct_lds_bytes<K, 2>());
-  set(reinterpret_cast<const void*>(&k_reconstruct_ragged<K, 4, 2>), reconstruct_lds_bytes<K, 4>());
-  set(reinterpret_cast<const void*>(&k_reconstruct_ragged<K, 4, 4>), reconstruct_lds_bytes<K, 4>());
-  set(reinterpret_cast<const void*>(&k_reconstruct_ragged<K, 8, 2>), reconstruct_lds_bytes<K, 8>());
-  set(reinterpret_cast<const void*>(&k_reconstruct_ragged<K, 8, 8>), reconstruct_lds_bytes<K, 8>());
-}
-
-hipError_t configure_ragged_kernels() {
-  hipError_t e = hipSuccess;
-  configure_ragged_k<64>(e);
-  configure_ragged_k<128>(e);
-  configure_ragged_k<256>(e);
-  return e;
-}
-
 }  // namespace
 
 bool ragged_encode_supported(uint32_t n, uint32_t k) {
@@ -2451,7 +2185,6 @@ hipError_t launch_reconstruct_ragged(const DevTables& T, const RaggedArgs& r, hi
 // `flags` are kernel parameters of their own: RaggedArgs is what the kernels
 // above take.  Every skip of the uniform kernels is kept, each exit
 // workgroup-uniform and before the barrier it would miss.
-// The last kernels of this file: every older kernel's assembly stays what it was.
 namespace {
 
 #if NP_BOUNDS_CHECK
@@ -2479,156 +2212,13 @@ __device__ __forceinline__ BoundsSet bounds_of_ragged_masked(const RaggedArgs& r
 template <int K>
 __global__ __launch_bounds__(4 * K) __attribute__((amdgpu_waves_per_eu(4))) void k_encode_masked_ragged(
     DevTables T, RaggedArgs r, const uint32_t* plan) {
-  using G = Geo<K>;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  uint8_t* tile = smem;
-  uint32_t* VP = reinterpret_cast<uint32_t*>(smem + G::kTileBytes);  // up to 4 staged transforms
-  const uint32_t nshift = r.n / K;
-  const uint32_t segw = static_cast<uint32_t>(restore_seg_words(r.n, K));
-  const uint32_t planw = static_cast<uint32_t>(restore_plan_words(r.n, K));
 #if NP_BOUNDS_CHECK
   bounds_arm(bounds_of_ragged_masked(r, T, plan, nullptr));
 #endif
   const RaggedHead h = ragged_head(r);
   if (h.item == kRaggedNoItem) return;  // padding of the plan
-  NP_BNOTE(plan + static_cast<size_t>(h.item) * planw, 4u * planw, kBkRecords);
-  const cpool_t seg = (cpool_t)(plan) + static_cast<size_t>(h.item) * planw;
-  const cpool_t rowbits = seg + segw;
-  const bool seg0 = (seg[0] & 1u) != 0;
-  const uint32_t first = next_segment(seg, 1, nshift);  // the first shift to run
-  if (!seg0 && first == nshift) return;                 // nothing to restore (or NeedMoreShards)
-  const uint8_t* pay = reinterpret_cast<const uint8_t*>(h.data);
-  const size_t payload_len = h.data_len, shard_len = h.shard_len;
-  uint8_t* const shards = reinterpret_cast<uint8_t*>(h.shards);
-  const uint32_t nchunks = static_cast<uint32_t>(shard_len / 2);
-  const uint32_t ch0 = h.tile * kTile;
-  const uint32_t ncols = min(static_cast<uint32_t>(kTile), nchunks - ch0);
-  uint8_t* out = shards + 2 * static_cast<size_t>(ch0);
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, g = uniform(tid >> 6);
-  const bool full = ncols == kTile && rows_vec_ok(shards, 0, shard_len);
-
-  // ---- tile load (as k_encode_fast)
-  {
-    const uint32_t c0 = tid / G::Q, m0 = tid % G::Q;
-    const uint32_t base = col_base<K>(c0) ^ (8u * m0);
-    const size_t gbase = static_cast<size_t>(ch0 + c0) * 2 * K + 8u * m0;
-    const bool fast = out_vec_ok(pay, 0) && static_cast<size_t>(ch0 + kTile) * 2 * K <= payload_len;
-    if (fast) {
-      uint2 v[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) v[i] = load_once(pay + gbase + static_cast<size_t>(i) * 32 * K);
-#pragma unroll
-      for (int i = 0; i < 16; ++i) *reinterpret_cast<uint2*>(tile + (base ^ col_base_c<K>(16u * i))) = v[i];
-    } else {
-#pragma unroll 1
-      for (uint32_t i = 0; i < 16; ++i) {
-        const size_t g0 = gbase + static_cast<size_t>(i) * 32 * K;
-        uint32_t w[2] = {0, 0};
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          if (g0 + e < payload_len) w[e >> 2] |= static_cast<uint32_t>(*NP_BCHK(pay + (g0 + e), 1, kBkPayloads)) << (8 * (e & 3));
-        *reinterpret_cast<uint2*>(tile + (base ^ col_base_c<K>(16u * i))) = make_uint2(w[0], w[1]);
-      }
-    }
-  }
-  const bool nt = rows_nt(shards, 0, shard_len);
-  // n <= 4K: one table buffer per transform that runs; otherwise two buffers
-  // alternate, each shift staging the next one that runs
-  const bool resident = nshift <= 4;
-  if (first < nshift) {
-    stage_vpools<K, G::kThreads>(T, 0, VP, true);  // inverse transform, index 0
-    if (resident) {
-      for (uint32_t sh = first; sh < nshift; sh = next_segment(seg, sh + 1, nshift))
-        stage_vpools<K, G::kThreads>(T, sh * K, VP + sh * G::kVPWords, true, enc_conv_u<K>(sh));
-    } else {
-      stage_vpools<K, G::kThreads>(T, first * K, VP + G::kVPWords, uniform_b(first < 4), enc_conv_u<K>(first));
-    }
-  }
-  __syncthreads();
-
-  const uint32_t cqb = col_base<K>(4 * lane) ^ (32u * g);  // blocks 4g..4g+3 of columns 4l..4l+3
-  // ---- cq pass: absent systematic rows, inverse levels 0..3
-  {
-    uint32_t CL[16], CH[16];
-    cq_read<K>(tile, cqb, CL, CH);
-    if (seg0) store_rows_masked(out, shard_len, 16 * g, restore_mask16(rowbits, 16 * g), CL, CH, lane, ncols, full, nt);
-    if (first == nshift) return;  // no parity row to restore
-    tower_convert(T, CL, CH);     // transforms run in tower coordinates
-    cq_levels<K, true, true, 0, false, kEncPrioCq>(T, VP, 0, g, CL, CH);
-    // the quad items overlay payload blocks that other waves read: wait for
-    // every wave's cq_read
-    __syncthreads();
-    cq_write_q(tile, g, lane, CL, CH);
-  }
-  __syncthreads();
-  // ---- high layout: inverse levels 4.. -> coefficients M
-  uint32_t ML[16], MH[16];
-  hi_read_q<K>(tile, g, lane, ML, MH);
-  hi_levels<K, true, true, 0, 0, kEncPrio>(T, VP, 0, ML, MH);
-#pragma unroll
-  for (int q = 0; q < 16; ++q) asm volatile("" : "+v"(ML[q]), "+v"(MH[q]));  // materialise M once
-
-  // top-level products of shift 1, then of shifts 1 ^ 2 (fwd_top); zero, so that
-  // a shift 2 without shift 1 accumulates into defined values (which nobody reads)
-  uint32_t PL[8] = {}, PH[8] = {};
-  uint32_t slot = 1;  // !resident: the table buffer of the shift that runs
-  // shift sh; nxt: the next shift that runs (nshift: none)
-  auto shift = [&](auto shc, uint32_t sh, uint32_t nxt) __attribute__((always_inline)) {
-    constexpr int SH = decltype(shc)::value;
-    constexpr int SHC = SH == kShift3Own ? 3 : SH;
-    const uint32_t index = sh * K;
-    uint32_t XL[16], XH[16];
-    const uint32_t* vp = VP + (resident ? sh : slot) * G::kVPWords;
-    if constexpr (SH == kShift3Own) {
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        XL[q] = ML[q];
-        XH[q] = MH[q];
-      }
-      fwd_top<K, 0, 0>(T, vp, index, XL, XH, PL, PH);
-      hi_levels<K, false, false, 1, 0, kEncPrio>(T, vp, index, XL, XH);
-    } else {
-      shift_hi<K, SH>(T, vp, index, ML, MH, XL, XH, PL, PH);
-    }
-    __syncthreads();  // the previous cq pass is done with the tile and with the other table buffer
-    if (!resident && nxt < nshift)
-      stage_vpools<K, G::kThreads>(T, nxt * K, VP + (slot ^ 1u) * G::kVPWords, uniform_b(nxt < 4),
-                                   enc_conv_u<K>(nxt));
-    hi_write_q<K>(tile, g, lane, XL, XH);
-    __syncthreads();
-    cq_read_q(tile, g, lane, XL, XH);
-    const uint32_t mask = restore_mask16(rowbits, index + 16 * g);
-    shift_cq_rows<K, SHC>(T, vp, index, g, XL, XH, mask);
-    store_rows_masked(out, shard_len, index + 16 * g, mask, XL, XH, lane, ncols, full, nt);
-    slot ^= 1u;
-  };
-  const bool own3 = ((seg[0] >> 1) & 3u) != 3u;  // shift 1 or 2 skipped
-  // cur: the next shift to run; nshift (2 at n = 2K: not "shift 2") when none is left
-  uint32_t cur = first;
-  if (cur == 1) {
-    const uint32_t nxt = next_segment(seg, 2, nshift);
-    shift(Int<1>{}, 1, nxt);
-    cur = nxt;
-  }
-  if (cur == 2 && cur < nshift) {
-    const uint32_t nxt = next_segment(seg, 3, nshift);
-    shift(Int<2>{}, 2, nxt);
-    cur = nxt;
-  }
-  if (cur == 3 && cur < nshift) {
-    const uint32_t nxt = next_segment(seg, 4, nshift);
-    if (own3)
-      shift(Int<kShift3Own>{}, 3, nxt);
-    else
-      shift(Int<3>{}, 3, nxt);
-    cur = nxt;
-  }
-#pragma unroll 1
-  while (cur < nshift) {
-    const uint32_t nxt = next_segment(seg, cur + 1, nshift);
-    shift(Int<0>{}, cur, nxt);
-    cur = nxt;
-  }
+  encode_planned<K>(T, smem, r.n, enc_tile(h), plan_of(plan, h.item, r.n, K), StoreRows{});
 }
 
 // One workgroup: one 256-column tile of one item, the present rows of the
@@ -2637,172 +2227,72 @@ __global__ __launch_bounds__(4 * K) __attribute__((amdgpu_waves_per_eu(4))) void
 template <int K>
 __global__ __launch_bounds__(4 * K) __attribute__((amdgpu_waves_per_eu(4))) void k_encode_verify_ragged(
     DevTables T, RaggedArgs r, const uint32_t* plan, uint8_t* flags) {
-  using G = Geo<K>;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  uint8_t* tile = smem;
-  uint32_t* VP = reinterpret_cast<uint32_t*>(smem + G::kTileBytes);  // up to 4 staged transforms
-  const uint32_t nshift = r.n / K;
-  const uint32_t segw = static_cast<uint32_t>(restore_seg_words(r.n, K));
-  const uint32_t planw = static_cast<uint32_t>(restore_plan_words(r.n, K));
 #if NP_BOUNDS_CHECK
   bounds_arm(bounds_of_ragged_masked(r, T, plan, flags));
 #endif
   const RaggedHead h = ragged_head(r);
   if (h.item == kRaggedNoItem) return;  // padding of the plan
-  NP_BNOTE(plan + static_cast<size_t>(h.item) * planw, 4u * planw, kBkRecords);
-  const cpool_t seg = (cpool_t)(plan) + static_cast<size_t>(h.item) * planw;
-  const cpool_t rowbits = seg + segw;
-  const uint32_t first = next_segment(seg, 1, nshift);  // the first shift to run
-  if (first == nshift) return;                          // no row to compare (or NeedMoreShards)
-  const uint8_t* pay = reinterpret_cast<const uint8_t*>(h.data);
-  const size_t payload_len = h.data_len, shard_len = h.shard_len;
-  const uint8_t* const shards = reinterpret_cast<const uint8_t*>(h.shards);
-  const uint32_t nchunks = static_cast<uint32_t>(shard_len / 2);
-  const uint32_t ch0 = h.tile * kTile;
-  const uint32_t ncols = min(static_cast<uint32_t>(kTile), nchunks - ch0);
-  const uint8_t* in = shards + 2 * static_cast<size_t>(ch0);
-  uint8_t* flag = flags + static_cast<size_t>(h.item) * r.n;
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, g = uniform(tid >> 6);
-  const bool full = ncols == kTile && rows_vec_ok(shards, 0, shard_len);
-
-  // ---- tile load (as k_encode_fast)
-  {
-    const uint32_t c0 = tid / G::Q, m0 = tid % G::Q;
-    const uint32_t base = col_base<K>(c0) ^ (8u * m0);
-    const size_t gbase = static_cast<size_t>(ch0 + c0) * 2 * K + 8u * m0;
-    const bool fast = out_vec_ok(pay, 0) && static_cast<size_t>(ch0 + kTile) * 2 * K <= payload_len;
-    if (fast) {
-      uint2 v[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) v[i] = load_once(pay + gbase + static_cast<size_t>(i) * 32 * K);
-#pragma unroll
-      for (int i = 0; i < 16; ++i) *reinterpret_cast<uint2*>(tile + (base ^ col_base_c<K>(16u * i))) = v[i];
-    } else {
-#pragma unroll 1
-      for (uint32_t i = 0; i < 16; ++i) {
-        const size_t g0 = gbase + static_cast<size_t>(i) * 32 * K;
-        uint32_t w[2] = {0, 0};
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          if (g0 + e < payload_len) w[e >> 2] |= static_cast<uint32_t>(*NP_BCHK(pay + (g0 + e), 1, kBkPayloads)) << (8 * (e & 3));
-        *reinterpret_cast<uint2*>(tile + (base ^ col_base_c<K>(16u * i))) = make_uint2(w[0], w[1]);
-      }
-    }
-  }
-  // n <= 4K: one table buffer per transform that runs; otherwise two buffers
-  // alternate, each shift staging the next one that runs
-  const bool resident = nshift <= 4;
-  stage_vpools<K, G::kThreads>(T, 0, VP, true);  // inverse transform, index 0
-  if (resident) {
-    for (uint32_t sh = first; sh < nshift; sh = next_segment(seg, sh + 1, nshift))
-      stage_vpools<K, G::kThreads>(T, sh * K, VP + sh * G::kVPWords, true, enc_conv_u<K>(sh));
-  } else {
-    stage_vpools<K, G::kThreads>(T, first * K, VP + G::kVPWords, uniform_b(first < 4), enc_conv_u<K>(first));
-  }
-  __syncthreads();
-
-  const uint32_t cqb = col_base<K>(4 * lane) ^ (32u * g);  // blocks 4g..4g+3 of columns 4l..4l+3
-  // ---- cq pass: inverse levels 0..3
-  {
-    uint32_t CL[16], CH[16];
-    cq_read<K>(tile, cqb, CL, CH);
-    tower_convert(T, CL, CH);  // transforms run in tower coordinates
-    cq_levels<K, true, true, 0, false, kEncPrioCq>(T, VP, 0, g, CL, CH);
-    // the quad items overlay payload blocks that other waves read: wait for
-    // every wave's cq_read
-    __syncthreads();
-    cq_write_q(tile, g, lane, CL, CH);
-  }
-  __syncthreads();
-  // ---- high layout: inverse levels 4.. -> coefficients M
-  uint32_t ML[16], MH[16];
-  hi_read_q<K>(tile, g, lane, ML, MH);
-  hi_levels<K, true, true, 0, 0, kEncPrio>(T, VP, 0, ML, MH);
-#pragma unroll
-  for (int q = 0; q < 16; ++q) asm volatile("" : "+v"(ML[q]), "+v"(MH[q]));  // materialise M once
-
-  // top-level products of shift 1, then of shifts 1 ^ 2 (fwd_top); zero, so that
-  // a shift 2 without shift 1 accumulates into defined values (which nobody reads)
-  uint32_t PL[8] = {}, PH[8] = {};
-  uint32_t slot = 1;  // !resident: the table buffer of the shift that runs
-  // shift sh; nxt: the next shift that runs (nshift: none)
-  auto shift = [&](auto shc, uint32_t sh, uint32_t nxt) __attribute__((always_inline)) {
-    constexpr int SH = decltype(shc)::value;
-    constexpr int SHC = SH == kShift3Own ? 3 : SH;
-    const uint32_t index = sh * K;
-    uint32_t XL[16], XH[16];
-    const uint32_t* vp = VP + (resident ? sh : slot) * G::kVPWords;
-    if constexpr (SH == kShift3Own) {
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        XL[q] = ML[q];
-        XH[q] = MH[q];
-      }
-      fwd_top<K, 0, 0>(T, vp, index, XL, XH, PL, PH);
-      hi_levels<K, false, false, 1, 0, kEncPrio>(T, vp, index, XL, XH);
-    } else {
-      shift_hi<K, SH>(T, vp, index, ML, MH, XL, XH, PL, PH);
-    }
-    __syncthreads();  // the previous cq pass is done with the tile and with the other table buffer
-    if (!resident && nxt < nshift)
-      stage_vpools<K, G::kThreads>(T, nxt * K, VP + (slot ^ 1u) * G::kVPWords, uniform_b(nxt < 4),
-                                   enc_conv_u<K>(nxt));
-    hi_write_q<K>(tile, g, lane, XL, XH);
-    __syncthreads();
-    cq_read_q(tile, g, lane, XL, XH);
-    const uint32_t mask = restore_mask16(rowbits, index + 16 * g);
-    shift_cq_rows<K, SHC>(T, vp, index, g, XL, XH, mask);
-    compare_rows_masked(in, shard_len, index + 16 * g, mask, XL, XH, lane, ncols, full, flag);
-    slot ^= 1u;
-  };
-  const bool own3 = ((seg[0] >> 1) & 3u) != 3u;  // shift 1 or 2 skipped
-  // cur: the next shift to run; nshift (2 at n = 2K: not "shift 2") when none is left
-  uint32_t cur = first;
-  if (cur == 1) {
-    const uint32_t nxt = next_segment(seg, 2, nshift);
-    shift(Int<1>{}, 1, nxt);
-    cur = nxt;
-  }
-  if (cur == 2 && cur < nshift) {
-    const uint32_t nxt = next_segment(seg, 3, nshift);
-    shift(Int<2>{}, 2, nxt);
-    cur = nxt;
-  }
-  if (cur == 3 && cur < nshift) {
-    const uint32_t nxt = next_segment(seg, 4, nshift);
-    if (own3)
-      shift(Int<kShift3Own>{}, 3, nxt);
-    else
-      shift(Int<3>{}, 3, nxt);
-    cur = nxt;
-  }
-#pragma unroll 1
-  while (cur < nshift) {
-    const uint32_t nxt = next_segment(seg, cur + 1, nshift);
-    shift(Int<0>{}, cur, nxt);
-    cur = nxt;
-  }
-}
-
-template <int K>
-void configure_ragged_masked_k(hipError_t& e) {
-  auto set = [&](const void* f, size_t bytes) {
-    hipError_t x = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
-    if (x != hipSuccess && e == hipSuccess) e = x;
-  };
-  set(reinterpret_cast<const void*>(&k_encode_masked_ragged<K>), encode_lds_bytes<K>());
-  set(reinterpret_cast<const void*>(&k_encode_verify_ragged<K>), encode_lds_bytes<K>());
-}
-
-hipError_t configure_ragged_masked_kernels() {
-  hipError_t e = hipSuccess;
-  configure_ragged_masked_k<64>(e);
-  configure_ragged_masked_k<128>(e);
-  configure_ragged_masked_k<256>(e);
-  return e;
+  encode_planned<K>(T, smem, r.n, enc_tile(h), plan_of(plan, h.item, r.n, K),
+                    CompareRows{flags + static_cast<size_t>(h.item) * r.n});
 }
 
 }  // namespace
+
+// The dynamic LDS of every kernel of this file (all above the 64 KiB default).
+hipError_t configure_fast_kernels() {
+  hipError_t e = hipSuccess;
+  auto set = [&](auto* f, size_t bytes) {
+    hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       static_cast<int>(bytes));
+    if (r != hipSuccess && e == hipSuccess) e = r;
+  };
+  set(&k_encode_fast<64>, encode_lds_bytes<64>());
+  set(&k_encode_fast<128>, encode_lds_bytes<128>());
+  set(&k_encode_fast<256>, encode_lds_bytes<256>());
+  set(&k_encode_multi<256>, encode_multi_lds_bytes<256>());
+  set(&k_reconstruct_fast<64, 2, 2>, reconstruct_lds_bytes<64, 2>());
+  set(&k_reconstruct_fast<64, 4, 2>, reconstruct_lds_bytes<64, 4>());
+  set(&k_reconstruct_fast<64, 4, 4>, reconstruct_lds_bytes<64, 4>());
+  set(&k_reconstruct_fast<128, 2, 2>, reconstruct_lds_bytes<128, 2>());
+  set(&k_reconstruct_fast<128, 4, 2>, reconstruct_lds_bytes<128, 4>());
+  set(&k_reconstruct_fast<128, 4, 4>, reconstruct_lds_bytes<128, 4>());
+  set(&k_reconstruct_fast<256, 2, 2>, reconstruct_lds_bytes<256, 2>());
+  set(&k_reconstruct_fast<256, 4, 2>, reconstruct_lds_bytes<256, 4>());
+  set(&k_reconstruct_fast<256, 4, 4>, reconstruct_lds_bytes<256, 4>());
+  set(&k_reconstruct_fast<64, 8, 2>, reconstruct_lds_bytes<64, 8>());
+  set(&k_reconstruct_fast<64, 8, 8>, reconstruct_lds_bytes<64, 8>());
+  set(&k_reconstruct_fast<128, 8, 2>, reconstruct_lds_bytes<128, 8>());
+  set(&k_reconstruct_fast<128, 8, 8>, reconstruct_lds_bytes<128, 8>());
+  set(&k_reconstruct_fast<256, 8, 2>, reconstruct_lds_bytes<256, 8>());
+  set(&k_reconstruct_fast<256, 8, 8>, reconstruct_lds_bytes<256, 8>());
+  // the single-tile encodes on plans and ragged batches, and the ragged decodes
+  set(&k_encode_masked<64>, encode_lds_bytes<64>());
+  set(&k_encode_masked<128>, encode_lds_bytes<128>());
+  set(&k_encode_masked<256>, encode_lds_bytes<256>());
+  set(&k_encode_verify<64>, encode_lds_bytes<64>());
+  set(&k_encode_verify<128>, encode_lds_bytes<128>());
+  set(&k_encode_verify<256>, encode_lds_bytes<256>());
+  auto ragged = [&](auto kc) {
+    constexpr int K = decltype(kc)::value;
+    set(&k_encode_ragged<K>, encode_lds_bytes<K>());
+    set(&k_reconstruct_ragged<K, 2, 2>, reconstruct_lds_bytes<K, 2>());
+    set(&k_reconstruct_ragged<K, 4, 2>, reconstruct_lds_bytes<K, 4>());
+    set(&k_reconstruct_ragged<K, 4, 4>, reconstruct_lds_bytes<K, 4>());
+    set(&k_reconstruct_ragged<K, 8, 2>, reconstruct_lds_bytes<K, 8>());
+    set(&k_reconstruct_ragged<K, 8, 8>, reconstruct_lds_bytes<K, 8>());
+  };
+  ragged(Int<64>{});
+  ragged(Int<128>{});
+  ragged(Int<256>{});
+  set(&k_encode_masked_ragged<64>, encode_lds_bytes<64>());
+  set(&k_encode_masked_ragged<128>, encode_lds_bytes<128>());
+  set(&k_encode_masked_ragged<256>, encode_lds_bytes<256>());
+  set(&k_encode_verify_ragged<64>, encode_lds_bytes<64>());
+  set(&k_encode_verify_ragged<128>, encode_lds_bytes<128>());
+  set(&k_encode_verify_ragged<256>, encode_lds_bytes<256>());
+  return e;
+}
 
 bool ragged_masked_supported(uint32_t n, uint32_t k) { return ragged_reconstruct_supported(n, k); }
 

@@ -19,13 +19,14 @@ namespace {
 
 constexpr uint32_t kPlanThreads = 256;
 
-// One workgroup per payload.  A wave takes 64 consecutive rows at a time (one
-// flag byte per lane, a ballot): two row words, and one bit of the segment
-// words (64 rows never straddle a segment: k >= 64).
-__global__ __launch_bounds__(kPlanThreads) void k_restore_plan(const uint8_t* __restrict__ present,
-                                                               const uint32_t* __restrict__ status, uint32_t n,
-                                                               uint32_t k, uint32_t wanted_n, size_t batch,
-                                                               uint32_t* __restrict__ plan) {
+// One workgroup per payload: the plan that marks the rows in [lo, hi) of a
+// decoded payload whose present flag is PRESENT.  A wave takes 64 consecutive
+// rows at a time (one flag byte per lane, a ballot): two row words, and one bit
+// of the segment words (64 rows never straddle a segment: k >= 64).
+template <bool PRESENT>
+__device__ __forceinline__ void plan_rows(const uint8_t* __restrict__ present, const uint32_t* __restrict__ status,
+                                          uint32_t n, uint32_t k, uint32_t lo, uint32_t hi, size_t batch,
+                                          uint32_t* __restrict__ plan) {
   __shared__ uint32_t seg[32];  // n / k <= 1024 segments
   const uint32_t pb = blockIdx.x, tid = threadIdx.x, lane = tid & 63u;
   const uint32_t segw = static_cast<uint32_t>(restore_seg_words(n, k));
@@ -49,8 +50,8 @@ __global__ __launch_bounds__(kPlanThreads) void k_restore_plan(const uint8_t* __
   uint32_t* pl = plan + static_cast<size_t>(pb) * words;
   for (uint32_t v0 = tid - lane; v0 < n; v0 += kPlanThreads) {  // n is a multiple of 64
     const uint32_t v = v0 + lane;
-    const bool absent = ok && v < wanted_n && *NP_BCHK(pres + v, 1, kBkPresent) == 0;
-    const uint64_t m = __ballot(absent);
+    const bool mark = ok && v >= lo && v < hi && (*NP_BCHK(pres + v, 1, kBkPresent) != 0) == PRESENT;
+    const uint64_t m = __ballot(mark);
     if (lane == 0) {
       *NP_BCHK(pl + segw + v0 / 32, 8, kBkRecords) = static_cast<uint32_t>(m);
       pl[segw + v0 / 32 + 1] = static_cast<uint32_t>(m >> 32);
@@ -59,6 +60,14 @@ __global__ __launch_bounds__(kPlanThreads) void k_restore_plan(const uint8_t* __
   }
   __syncthreads();
   if (tid < segw) *NP_BCHK(pl + tid, 4, kBkRecords) = seg[tid];
+}
+
+// The restore's plan: the absent rows below wanted_n.
+__global__ __launch_bounds__(kPlanThreads) void k_restore_plan(const uint8_t* __restrict__ present,
+                                                               const uint32_t* __restrict__ status, uint32_t n,
+                                                               uint32_t k, uint32_t wanted_n, size_t batch,
+                                                               uint32_t* __restrict__ plan) {
+  plan_rows<false>(present, status, n, k, 0, wanted_n, batch, plan);
 }
 
 constexpr uint32_t kCopyWaves = 4;
@@ -141,8 +150,7 @@ hipError_t launch_copy_absent_rows(const uint8_t* src, size_t sstride, uint8_t* 
 
 // ------------------------------------------------------------- verify ----
 // np_verify_shards_batch_dev (engine.cpp launch_verify): the same flow with
-// "present" in place of "absent" and a compare in place of the store.  These
-// kernels come after the restore's, whose code objects stay what they were.
+// "present" in place of "absent" and a compare in place of the store.
 //
 //  * k_verify_plan -- the plan of kernels_fast.hip k_encode_verify: bit v set
 //    when row v is present, in [k, wanted_n), and the payload decoded.  Present
@@ -157,43 +165,12 @@ hipError_t launch_copy_absent_rows(const uint8_t* src, size_t sstride, uint8_t* 
 //    count does not depend on any order.
 namespace {
 
+// The verify's plan: the present rows in [k, wanted_n).
 __global__ __launch_bounds__(kPlanThreads) void k_verify_plan(const uint8_t* __restrict__ present,
                                                               const uint32_t* __restrict__ status, uint32_t n,
                                                               uint32_t k, uint32_t wanted_n, size_t batch,
                                                               uint32_t* __restrict__ plan) {
-  __shared__ uint32_t seg[32];  // n / k <= 1024 segments
-  const uint32_t pb = blockIdx.x, tid = threadIdx.x, lane = tid & 63u;
-  const uint32_t segw = static_cast<uint32_t>(restore_seg_words(n, k));
-  const size_t words = restore_plan_words(n, k);
-#if NP_BOUNDS_CHECK
-  {
-    BoundsSet b{};
-    b.lo[kBkPresent] = reinterpret_cast<uint64_t>(present);
-    b.hi[kBkPresent] = b.lo[kBkPresent] + batch * n;
-    b.lo[kBkStatus] = reinterpret_cast<uint64_t>(status);
-    b.hi[kBkStatus] = b.lo[kBkStatus] + batch * 8;
-    b.lo[kBkRecords] = reinterpret_cast<uint64_t>(plan);
-    b.hi[kBkRecords] = b.lo[kBkRecords] + batch * words * 4;
-    bounds_arm(b);
-  }
-#endif
-  if (tid < 32) seg[tid] = 0;
-  __syncthreads();
-  const bool ok = *NP_BCHK(status + 2 * static_cast<size_t>(pb), 4, kBkStatus) == 0;
-  const uint8_t* pres = present + static_cast<size_t>(pb) * n;
-  uint32_t* pl = plan + static_cast<size_t>(pb) * words;
-  for (uint32_t v0 = tid - lane; v0 < n; v0 += kPlanThreads) {  // n is a multiple of 64
-    const uint32_t v = v0 + lane;
-    const bool cmp = ok && v >= k && v < wanted_n && *NP_BCHK(pres + v, 1, kBkPresent) != 0;
-    const uint64_t m = __ballot(cmp);
-    if (lane == 0) {
-      *NP_BCHK(pl + segw + v0 / 32, 8, kBkRecords) = static_cast<uint32_t>(m);
-      pl[segw + v0 / 32 + 1] = static_cast<uint32_t>(m >> 32);
-      if (m) atomicOr(&seg[(v0 / k) >> 5], 1u << ((v0 / k) & 31u));
-    }
-  }
-  __syncthreads();
-  if (tid < segw) *NP_BCHK(pl + tid, 4, kBkRecords) = seg[tid];
+  plan_rows<true>(present, status, n, k, k, wanted_n, batch, plan);
 }
 
 // One wave per 4 KiB piece of a row in [k, rows) (as k_copy_absent_rows): enc
