@@ -148,6 +148,19 @@ int np_rs_restore_shards(np_ctx* ctx, const np_code_params* params, const uint8_
  * mismatching row, or NULL. */
 int np_rs_verify_shards(np_ctx* ctx, const np_code_params* params, const uint8_t* const* shards,
                         const size_t* shard_lens, size_t n_received, size_t* bad_rows, uint8_t* mismatch);
+/* np_recover_batch_dev for one payload in host memory, staged as
+ * np_rs_restore_shards stages it: shards/shard_lens/n_received as
+ * np_rs_reconstruct (same validation, same errors -- NP_ERR_NEED_MORE_SHARDS is
+ * a return status; odd lengths zero padded).  Three output groups, each
+ * optional through NULL, at least one required:
+ *   out / out_capacity / out_len   the payload, as np_rs_reconstruct;
+ *   restored / restored_len        the absent rows, as np_rs_restore_shards;
+ *   bad_rows / mismatch            the verdict, as np_rs_verify_shards
+ *                                  (mismatch needs bad_rows).
+ * One staging of the rows and one decode serve all of them. */
+int np_rs_recover(np_ctx* ctx, const np_code_params* params, const uint8_t* const* shards, const size_t* shard_lens,
+                  size_t n_received, uint8_t* out, size_t out_capacity, size_t* out_len, uint8_t* const* restored,
+                  size_t restored_len, size_t* bad_rows, uint8_t* mismatch);
 /* mod.rs:247-285 ReedSolomon::reconstruct_from_systematic (first k shards, all present). */
 int np_rs_reconstruct_from_systematic(np_ctx* ctx, const np_code_params* params, const uint8_t* const* chunks,
                                       const size_t* chunk_lens, size_t n_chunks, uint8_t* out,
@@ -269,6 +282,37 @@ int np_restore_shards_batch_dev(np_ctx* ctx, const np_code_params* params, uint8
 int np_verify_shards_batch_dev(np_ctx* ctx, const np_code_params* params, const uint8_t* d_shards, size_t shard_len,
                                size_t batch_stride, const uint8_t* d_present, size_t batch, uint32_t* d_bad_rows,
                                uint8_t* d_mismatch, np_payload_status* d_status, void* stream);
+/* The payload, the missing shards and the verdict from one decode: what
+ * np_reconstruct_batch_dev3 (d_locators = NULL), np_restore_shards_batch_dev
+ * and np_verify_shards_batch_dev give on the same received rows, each output
+ * bit for bit what the separate call produces, for any received bytes.
+ *   d_out / out_stride  (d_out may be NULL) the payloads, (shard_len/2)*2k bytes
+ *               each at out_stride;
+ *   restore     != 0: the absent rows below wanted_n are written into d_shards
+ *               and no other byte of it; == 0: d_shards is only read;
+ *   d_bad_rows / d_mismatch  (d_bad_rows may be NULL: no verify; d_mismatch may
+ *               be NULL) as np_verify_shards_batch_dev: the present rows in
+ *               [k, wanted_n) against E.  Restored rows are absent and compared
+ *               rows present: the verdict is that of the received rows;
+ *   d_status    (may be NULL) as in the three calls.
+ * A payload with < k present rows gets NP_ERR_NEED_MORE_SHARDS in d_status,
+ * UINT32_MAX in d_bad_rows and an all-zero map; its d_out bytes and its rows are
+ * left untouched.  An output that was not requested is never written.
+ * Validation as np_restore_shards_batch_dev, and NP_ERR_INVALID_ARGUMENT when
+ * nothing is requested (d_out == NULL, restore == 0, d_bad_rows == NULL), when
+ * d_mismatch comes without d_bad_rows, or when d_out comes with out_stride <
+ * (shard_len/2)*2k.  batch == 0 returns NP_OK and launches nothing.
+ * Asynchronous on stream.  d_out must not overlap d_shards.
+ * With d_out the decode goes straight to the caller's buffer: the context then
+ * keeps no payloads, and for k in {64, 128, 256} the batch is not sliced.  For
+ * those k a call that restores and verifies runs one encode that stores the
+ * absent rows and compares the present ones as it produces them; with one of
+ * the two it runs that call's encode.  Every other shape: the ordinary encode
+ * into context scratch once, then the copy and / or the compare. */
+int np_recover_batch_dev(np_ctx* ctx, const np_code_params* params, uint8_t* d_shards, size_t shard_len,
+                         size_t batch_stride, const uint8_t* d_present, size_t batch, uint8_t* d_out,
+                         size_t out_stride, int restore, uint32_t* d_bad_rows, uint8_t* d_mismatch,
+                         np_payload_status* d_status, void* stream);
 /* ---- ragged device batches: one call for payloads of different lengths -----
  * One entry per payload (item).  The same array serves an encode and then the
  * reconstruct of its shards.  `items` is HOST memory, read before the call

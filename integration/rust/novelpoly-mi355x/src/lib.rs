@@ -287,6 +287,62 @@ impl ReedSolomon {
 		Ok(bad == 0)
 	}
 
+	/// `reconstruct`, `restore_shards` and `mismatched_shards` from one staging
+	/// and one decode of `received_shards` (np_rs_recover): the payload, all
+	/// `wanted_n` shards and the indices of the received shards that differ
+	/// from the re-encoding.  Same errors as `reconstruct`.
+	pub fn recover<S: Shard>(&self, received_shards: Vec<Option<S>>) -> Result<(Vec<u8>, Vec<S>, Vec<usize>)> {
+		let (ptrs, lens) = shard_views(&received_shards);
+		let wanted_n = self.params.raw.wanted_n;
+		let max_syms = lens.iter().take(self.params.raw.n).map(|l| (l + 1) / 2).max().unwrap_or(0);
+		let sl = 2 * max_syms;
+		let mut out = vec![0u8; (max_syms * 2 * self.params.raw.k).max(1)];
+		let mut out_len = 0usize;
+		let mut restored: Vec<Vec<u8>> = (0..wanted_n)
+			.map(|i| if ptrs.get(i).map_or(true, |p| p.is_null()) { vec![0u8; sl.max(1)] } else { Vec::new() })
+			.collect();
+		let outs: Vec<*mut u8> =
+			restored.iter_mut().map(|r| if r.is_empty() { std::ptr::null_mut() } else { r.as_mut_ptr() }).collect();
+		let mut bad = 0usize;
+		let mut flags = vec![0u8; self.params.raw.n.max(1)];
+		check(unsafe {
+			sys::np_rs_recover(
+				self.ctx.raw,
+				&self.params.raw,
+				ptrs.as_ptr(),
+				lens.as_ptr(),
+				ptrs.len(),
+				out.as_mut_ptr(),
+				out.len(),
+				&mut out_len,
+				outs.as_ptr(),
+				sl,
+				&mut bad,
+				flags.as_mut_ptr(),
+			)
+		})?;
+		out.truncate(out_len);
+		let mut received = received_shards;
+		received.resize_with(wanted_n, || None);
+		let shards = received
+			.into_iter()
+			.zip(restored)
+			.map(|(have, mut got)| match have {
+				Some(s) => {
+					let mut v = AsRef::<[u8]>::as_ref(&s).to_vec();
+					v.resize(sl, 0);
+					S::from(v)
+				}
+				None => {
+					got.truncate(sl);
+					S::from(got)
+				}
+			})
+			.collect();
+		let rows = flags.iter().enumerate().filter(|(_, f)| **f != 0).map(|(i, _)| i).collect();
+		Ok((out, shards, rows))
+	}
+
 	/// mod.rs:247-285: the first k shards, all present.
 	pub fn reconstruct_from_systematic<S: Shard>(&self, chunks: Vec<S>) -> Result<Vec<u8>> {
 		let ptrs: Vec<*const u8> = chunks.iter().map(|c| AsRef::<[u8]>::as_ref(c).as_ptr()).collect();

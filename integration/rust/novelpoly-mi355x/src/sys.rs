@@ -151,6 +151,36 @@ extern "C" {
 		d_status: *mut np_payload_status,
 		stream: *mut c_void,
 	) -> c_int;
+	pub fn np_rs_recover(
+		ctx: *mut np_ctx,
+		params: *const np_code_params,
+		shards: *const *const u8,
+		shard_lens: *const usize,
+		n_received: usize,
+		out: *mut u8,
+		out_capacity: usize,
+		out_len: *mut usize,
+		restored: *const *mut u8,
+		restored_len: usize,
+		bad_rows: *mut usize,
+		mismatch: *mut u8,
+	) -> c_int;
+	pub fn np_recover_batch_dev(
+		ctx: *mut np_ctx,
+		params: *const np_code_params,
+		d_shards: *mut u8,
+		shard_len: usize,
+		batch_stride: usize,
+		d_present: *const u8,
+		batch: usize,
+		d_out: *mut u8,
+		out_stride: usize,
+		restore: c_int,
+		d_bad_rows: *mut u32,
+		d_mismatch: *mut u8,
+		d_status: *mut np_payload_status,
+		stream: *mut c_void,
+	) -> c_int;
 	pub fn np_encode_ragged_dev(
 		ctx: *mut np_ctx,
 		params: *const np_code_params,

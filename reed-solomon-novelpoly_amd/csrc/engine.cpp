@@ -658,7 +658,7 @@ int np_debug_bounds_check(np_ctx* c, uint32_t out[8]) {
   return NP_OK;
 }
 
-const char* np_version(void) { return "novelpoly-mi355x 0.4.0 (gfx950)"; }
+const char* np_version(void) { return "novelpoly-mi355x 0.5.0 (gfx950)"; }
 
 size_t np_recoverability_subset_size(size_t n) { return (n ? (n - 1) / 3 : 0) + 1; }
 
@@ -1425,49 +1425,61 @@ hipError_t restore_scratch(np_ctx* c, size_t want, hipStream_t s, uint8_t** out)
   return e;
 }
 
-// What a uniform restore / verify call fixes for all its slices: whether the
-// row-masked encodes serve (n, k); per payload the decoded bytes, the scratch
-// shard rows (!direct) and the plan bytes (direct); the payloads per slice.
+// What a uniform restore / verify / recover call fixes for all its slices:
+// whether the row-masked encodes serve (n, k); per payload the decoded bytes,
+// those of them kept in scratch (none when the caller's buffer takes the
+// decode), the scratch shard rows (!direct) and the plan bytes (direct); the
+// payloads per slice.
 struct MaskedShape {
   uint32_t n, k, wanted_n;
   bool direct;
-  size_t pay_len, rows_len, plan_len, per;
+  size_t pay_len, scr_pay, rows_len, plan_len, per;
 };
 
-MaskedShape masked_shape(const np_ctx* c, const np_code_params* p, size_t shard_len) {
+// own_payload: the decode goes to context scratch; both: the plan of a call that
+// restores and verifies (np::recover_plan_words).
+MaskedShape masked_shape(const np_ctx* c, const np_code_params* p, size_t shard_len, bool own_payload = true,
+                         bool both = false) {
   MaskedShape m{};
   m.n = static_cast<uint32_t>(p->n), m.k = static_cast<uint32_t>(p->k), m.wanted_n = static_cast<uint32_t>(p->wanted_n);
   m.direct = np::masked_encode_supported(m.n, m.k);
   m.pay_len = (shard_len / 2) * 2 * p->k;
+  m.scr_pay = own_payload ? m.pay_len : 0;
   m.rows_len = m.direct ? 0 : p->wanted_n * shard_len;
-  m.plan_len = m.direct ? np::restore_plan_words(m.n, m.k) * sizeof(uint32_t) : 0;
+  m.plan_len = !m.direct ? 0 : (both ? np::recover_plan_words(m.n, m.k) : np::restore_plan_words(m.n, m.k)) * sizeof(uint32_t);
   // The cap bounds the decoded payloads of a slice, and its scratch shard rows
   // likewise (the plan and status come on top: bytes per payload).  Slices are
   // multiples of 8 payloads where they can be: the fast kernels place a
   // payload's tiles on one XCD only then (fast_common.hpp tile_of), and a slice
-  // of 1023 measured 1.5-1.7 x the reconstruct time of one of 1024.
-  m.per = c->restore_cap / std::max(m.pay_len, m.rows_len);
+  // of 1023 measured 1.5-1.7 x the reconstruct time of one of 1024.  A call that
+  // keeps neither in scratch is not sliced.
+  const size_t big = std::max(m.scr_pay, m.rows_len);
+  m.per = big ? c->restore_cap / big : ~size_t(7);
   m.per = m.per >= 8 ? m.per & ~size_t(7) : std::max<size_t>(1, m.per);
   return m;
 }
 
-// One slice of a uniform restore / verify: payloads [b0, b0 + cnt) decoded to
-// the head of the restore scratch.
+// One slice of a uniform restore / verify / recover: payloads [b0, b0 + cnt)
+// decoded to the head of the restore scratch, or to the caller's buffer.
 struct MaskedSlice {
   size_t cnt = 0;
-  uint8_t *scr = nullptr, *rows = nullptr, *flags = nullptr;  // payloads; !direct: shard rows; own flag map
+  uint8_t *scr = nullptr, *rows = nullptr, *flags = nullptr;  // scratch (payloads first); !direct: shard rows; own flag map
   uint32_t* plan = nullptr;
+  const uint8_t* pay = nullptr;  // the decoded payloads, pay_stride apart
+  size_t pay_stride = 0;
   np::ReconstructArgs a{};
 };
 
-// Lays out the scratch of the slice at b0 and reconstructs its payloads into it.
+// Lays out the scratch of the slice at b0 and reconstructs its payloads into it,
+// or into d_out (payload b at d_out + b * out_stride) when that is given.
 // `own_flags`: bytes per payload of a flag map of the call's own (verify
 // without d_mismatch).
 hipError_t masked_reconstruct(np_ctx* c, const np_code_params* p, const MaskedShape& m, const uint8_t* d_shards,
                               size_t shard_len, size_t bstride, const uint8_t* d_present, size_t b0, size_t batch,
-                              uint32_t* d_status, size_t own_flags, hipStream_t s, MaskedSlice* sl) {
+                              uint32_t* d_status, size_t own_flags, hipStream_t s, MaskedSlice* sl,
+                              uint8_t* d_out = nullptr, size_t out_stride = 0) {
   const size_t cnt = std::min(m.per, batch - b0), own_status = d_status ? 0 : kStatusBytes;
-  const size_t o_rows = align256(cnt * m.pay_len), o_plan = o_rows + align256(cnt * m.rows_len);
+  const size_t o_rows = align256(cnt * m.scr_pay), o_plan = o_rows + align256(cnt * m.rows_len);
   const size_t o_status = o_plan + align256(cnt * m.plan_len), o_flags = o_status + align256(cnt * own_status);
   hipError_t e = restore_scratch(c, o_flags + align256(cnt * own_flags), s, &sl->scr);
   if (e != hipSuccess) return e;
@@ -1475,7 +1487,10 @@ hipError_t masked_reconstruct(np_ctx* c, const np_code_params* p, const MaskedSh
   sl->rows = sl->scr + o_rows;
   sl->plan = reinterpret_cast<uint32_t*>(sl->scr + o_plan);
   sl->flags = sl->scr + o_flags;
-  sl->a = rec_args(p, d_shards + b0 * bstride, shard_len, bstride, d_present + b0 * p->n, cnt, sl->scr, m.pay_len,
+  uint8_t* out = d_out ? d_out + b0 * out_stride : sl->scr;
+  sl->pay = out;
+  sl->pay_stride = d_out ? out_stride : m.pay_len;
+  sl->a = rec_args(p, d_shards + b0 * bstride, shard_len, bstride, d_present + b0 * p->n, cnt, out, sl->pay_stride,
                    d_status ? d_status + 2 * b0 : reinterpret_cast<uint32_t*>(sl->scr + o_status));
   return launch_reconstruct(c, sl->a, s);
 }
@@ -1557,7 +1572,80 @@ hipError_t launch_verify(np_ctx* c, const np_code_params* p, const uint8_t* d_sh
   return hipSuccess;
 }
 
+// np_recover_batch_dev after validation: what launch_restore and launch_verify
+// do, and the payload, from one reconstruct per slice.  With d_out the decode
+// goes straight to the caller's buffer, which is then the encode's payload
+// source: no payload scratch, and a direct shape runs unsliced.  A direct shape
+// with one request runs that request's plan and encode unchanged; with both, one
+// plan (np::launch_recover_plan) and one encode that stores the absent rows and
+// compares the present ones.  Every other shape encodes into scratch rows once
+// and copies and / or compares from them.  Caller holds the context lock.
+hipError_t launch_recover(np_ctx* c, const np_code_params* p, uint8_t* d_shards, size_t shard_len, size_t bstride,
+                          const uint8_t* d_present, size_t batch, uint8_t* d_out, size_t out_stride, bool restore,
+                          uint32_t* d_bad_rows, uint8_t* d_mismatch, uint32_t* d_status, hipStream_t s) {
+  const bool verify = d_bad_rows != nullptr;
+  if (!restore && !verify)  // the payload alone: np_reconstruct_batch_dev3 with d_locators = NULL
+    return launch_reconstruct(c, rec_args(p, d_shards, shard_len, bstride, d_present, batch, d_out, out_stride, d_status), s);
+  const MaskedShape m = masked_shape(c, p, shard_len, d_out == nullptr, restore && verify);
+  // the encode runs when a request has a row it can name: the restore any row
+  // below wanted_n, the verify those in [k, wanted_n)
+  const bool do_restore = restore && m.wanted_n, do_verify = verify && m.wanted_n > m.k;
+  for (size_t b0 = 0; b0 < batch; b0 += m.per) {
+    MaskedSlice sl;
+    hipError_t e = masked_reconstruct(c, p, m, d_shards, shard_len, bstride, d_present, b0, batch, d_status,
+                                      verify && !d_mismatch ? p->n : 0, s, &sl, d_out, out_stride);
+    uint8_t* shards = d_shards + b0 * bstride;
+    uint8_t* flags = d_mismatch ? d_mismatch + b0 * p->n : sl.flags;
+    if (e == hipSuccess && verify) e = HIP(hipMemsetAsync(flags, 0, sl.cnt * p->n, s));
+    if (e == hipSuccess && (do_restore || do_verify)) {
+      if (m.direct) {
+        const np::EncodeArgs ea = enc_args(p, sl.pay, m.pay_len, sl.pay_stride, sl.cnt, shards, bstride);
+        if (restore && verify) {
+          e = HIP(np::launch_recover_plan(sl.a.present, sl.a.status, m.n, m.k, m.wanted_n, sl.cnt, sl.plan, s));
+          if (e == hipSuccess) e = HIP(np::launch_encode_recover(c->T, ea, sl.plan, flags, s));
+        } else if (restore) {
+          e = HIP(np::launch_restore_plan(sl.a.present, sl.a.status, m.n, m.k, m.wanted_n, sl.cnt, sl.plan, s));
+          if (e == hipSuccess) e = HIP(np::launch_encode_masked(c->T, ea, sl.plan, s));
+        } else {  // (do_verify; the verify encode only reads the rows)
+          e = HIP(np::launch_verify_plan(sl.a.present, sl.a.status, m.n, m.k, m.wanted_n, sl.cnt, sl.plan, s));
+          if (e == hipSuccess) e = HIP(np::launch_encode_verify(c->T, ea, sl.plan, flags, s));
+        }
+      } else {
+        e = launch_encode(c, enc_args(p, sl.pay, m.pay_len, sl.pay_stride, sl.cnt, sl.rows, m.rows_len), s);
+        if (e == hipSuccess && do_restore)
+          e = HIP(np::launch_copy_absent_rows(sl.rows, m.rows_len, shards, bstride, shard_len, sl.a.present,
+                                              sl.a.status, m.n, m.wanted_n, sl.cnt, s));
+        if (e == hipSuccess && do_verify)
+          e = HIP(np::launch_compare_present_rows(sl.rows, m.rows_len, shards, bstride, shard_len, sl.a.present,
+                                                  sl.a.status, m.n, m.k, m.wanted_n, sl.cnt, flags, s));
+      }
+    }
+    if (e == hipSuccess && verify) e = HIP(np::launch_verify_summary(flags, sl.a.status, m.n, sl.cnt, d_bad_rows + b0, s));
+    e = masked_done(c, s, e);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 }  // namespace
+
+int np_recover_batch_dev(np_ctx* c, const np_code_params* p, uint8_t* d_shards, size_t shard_len, size_t bstride,
+                         const uint8_t* d_present, size_t batch, uint8_t* d_out, size_t out_stride, int restore,
+                         uint32_t* d_bad_rows, uint8_t* d_mismatch, np_payload_status* d_status, void* stream) {
+  if (!c) return fail(NP_ERR_INVALID_ARGUMENT);
+  int st = check_params(p);
+  if (st) return st;
+  if (shard_len == 0 || (shard_len & 1)) return fail(NP_ERR_EMPTY_SHARD);
+  if (!d_shards || !d_present || bstride < p->n * shard_len) return fail(NP_ERR_INVALID_ARGUMENT);
+  if ((!d_out && !restore && !d_bad_rows) || (d_mismatch && !d_bad_rows) ||
+      (d_out && out_stride < (shard_len / 2) * 2 * p->k))
+    return fail(NP_ERR_INVALID_ARGUMENT);
+  if (batch == 0) return NP_OK;
+  std::lock_guard<std::mutex> g(c->mu);  // context scratch
+  (void)hipSetDevice(c->device);
+  return dev_err(launch_recover(c, p, d_shards, shard_len, bstride, d_present, batch, d_out, out_stride, restore != 0,
+                                d_bad_rows, d_mismatch, reinterpret_cast<uint32_t*>(d_status), pick(c, stream)));
+}
 
 int np_verify_shards_batch_dev(np_ctx* c, const np_code_params* p, const uint8_t* d_shards, size_t shard_len,
                                size_t bstride, const uint8_t* d_present, size_t batch, uint32_t* d_bad_rows,
@@ -1828,6 +1916,86 @@ int np_rs_verify_shards(np_ctx* c, const np_code_params* p, const uint8_t* const
   if (count == UINT32_MAX) return fail(NP_ERR_NEED_MORE_SHARDS, have, k, n);  // (caught above: have >= k decodes)
   *bad_rows = count;
   if (mismatch) std::memcpy(mismatch, res + o_map, n);
+  return NP_OK;
+}
+
+int np_rs_recover(np_ctx* c, const np_code_params* p, const uint8_t* const* shards, const size_t* lens,
+                  size_t n_received, uint8_t* out, size_t cap, size_t* out_len, uint8_t* const* restored,
+                  size_t restored_len, size_t* bad_rows, uint8_t* mismatch) {
+  // validation as np_rs_reconstruct (mod.rs:163-214)
+  if (!c || !p || (n_received && (!shards || !lens))) return fail(NP_ERR_INVALID_ARGUMENT);
+  if ((!out && !restored && !bad_rows) || (mismatch && !bad_rows)) return fail(NP_ERR_INVALID_ARGUMENT);
+  if (!is_pow2(p->n) && !is_pow2(p->k)) return fail(NP_ERR_PARAMETER_MUST_BE_POWER_OF_2, p->n, p->k);
+  const size_t n = p->n, k = p->k;
+  std::vector<uint8_t> present(n, 0);
+  size_t have = 0;
+  for (size_t i = 0; i < n && i < n_received; ++i) {
+    present[i] = shards[i] ? 1 : 0;
+    have += present[i];
+  }
+  if (have < k) return fail(NP_ERR_NEED_MORE_SHARDS, have, k, n);
+  size_t first = 0;
+  while (!present[first]) ++first;
+  const size_t syms = (lens[first] + 1) / 2;
+  if (syms == 0) return fail(NP_ERR_EMPTY_SHARD);
+  for (size_t i = first + 1; i < n; ++i)
+    if (present[i] && (lens[i] + 1) / 2 != syms) return fail(NP_ERR_INCONSISTENT_SHARD_LENGTHS, syms, (lens[i] + 1) / 2);
+  int st = check_params(p);
+  if (st) return st;
+  const size_t sl = 2 * syms, need = syms * 2 * k;
+  if (out && (!out_len || cap < need)) return fail(NP_ERR_INVALID_ARGUMENT, need);
+  if (restored && restored_len < sl) return fail(NP_ERR_INVALID_ARGUMENT, sl);
+  std::lock_guard<std::mutex> g(c->mu);
+  (void)hipSetDevice(c->device);
+  // results: the payload, then (256-aligned) the count, then (256 bytes on) the n flags
+  const size_t o_cnt = out ? align256(need) : 0, o_map = o_cnt + 256, res_bytes = o_map + n;
+  hipError_t e = HIP(c->h_in.ensure(n * sl));
+  if (e == hipSuccess) e = HIP(c->d_in.ensure(n * sl));
+  if (e == hipSuccess) e = HIP(c->d_present.ensure(n));
+  if (e == hipSuccess) e = HIP(c->h_pres.ensure(n));
+  if (e == hipSuccess) e = HIP(c->d_out.ensure(res_bytes));
+  if (e == hipSuccess) e = HIP(c->h_out.ensure(res_bytes));
+  if (e != hipSuccess) return dev_err(e);
+  std::memcpy(c->h_pres.p, present.data(), n);
+  uint8_t* stage = c->h_in.as<uint8_t>();
+  for (size_t i = 0; i < n; ++i) {
+    uint8_t* row = stage + i * sl;
+    if (present[i]) {
+      std::memcpy(row, shards[i], lens[i]);
+      if (lens[i] < sl) std::memset(row + lens[i], 0, sl - lens[i]);  // WrappedShard zero pad
+    } else {
+      std::memset(row, 0, sl);
+    }
+  }
+  hipStream_t s = c->stream;
+  uint8_t* d_res = c->d_out.as<uint8_t>();
+  e = HIP(hipMemcpyAsync(c->d_in.p, stage, n * sl, hipMemcpyHostToDevice, s));
+  if (e == hipSuccess) e = HIP(hipMemcpyAsync(c->d_present.p, c->h_pres.p, n, hipMemcpyHostToDevice, s));
+  if (e == hipSuccess)
+    e = launch_recover(c, p, c->d_in.as<uint8_t>(), sl, n * sl, c->d_present.as<uint8_t>(), 1, out ? d_res : nullptr,
+                       need, restored != nullptr, bad_rows ? reinterpret_cast<uint32_t*>(d_res + o_cnt) : nullptr,
+                       bad_rows ? d_res + o_map : nullptr, nullptr, s);
+  if (e == hipSuccess && (out || bad_rows))
+    e = HIP(hipMemcpyAsync(c->h_out.p, d_res, res_bytes, hipMemcpyDeviceToHost, s));
+  // the rows come back through the same pinned staging (the received ones unchanged)
+  if (e == hipSuccess && restored) e = HIP(hipMemcpyAsync(stage, c->d_in.p, p->wanted_n * sl, hipMemcpyDeviceToHost, s));
+  if (e == hipSuccess) e = HIP(hipStreamSynchronize(s));
+  if (e != hipSuccess) return dev_err(e);
+  const uint8_t* res = c->h_out.as<uint8_t>();
+  if (bad_rows) {
+    uint32_t count = 0;
+    std::memcpy(&count, res + o_cnt, sizeof(count));
+    if (count == UINT32_MAX) return fail(NP_ERR_NEED_MORE_SHARDS, have, k, n);  // (caught above: have >= k decodes)
+    *bad_rows = count;
+    if (mismatch) std::memcpy(mismatch, res + o_map, n);
+  }
+  if (out) {
+    std::memcpy(out, res, need);
+    *out_len = need;
+  }
+  if (restored)
+    for (size_t i = 0; i < p->wanted_n; ++i)
+      if (!present[i] && restored[i]) std::memcpy(restored[i], stage + i * sl, sl);
   return NP_OK;
 }
 

@@ -2239,6 +2239,81 @@ __global__ __launch_bounds__(4 * K) __attribute__((amdgpu_waves_per_eu(4))) void
 
 }  // namespace
 
+// -------------------------------------------------------- recover encode ----
+// np_recover_batch_dev with the restore and the verify requested: one pass over
+// the re-encoding of the reconstructed payload that stores the absent rows
+// below wanted_n into a.shards (k_encode_masked's part) and compares the present
+// rows in [K, wanted_n) with a.shards (k_encode_verify's part).  The plan
+// (k_recover_plan, launchers.hpp recover_plan_words) marks the union of the two
+// in the words encode_planned reads, so that a segment or a butterfly group is
+// skipped only when neither purpose needs it; a further array of row words says
+// which rows of the union are stored.  A row is stored or compared, never both:
+// the stores touch absent rows only, the loads present rows only, so no
+// workgroup reads what another writes.
+// (Behind the ragged kernels in the file and in configure_fast_kernels, so that
+// every older kernel keeps its place and its assembler-local label numbers in
+// the code object: tools/isa_funcdiff.py against the parent lists the new
+// instances alone.)
+namespace {
+
+// encode_planned's sink of the recover.  The compare goes first: its loads are
+// what the wave waits for, while the stores need no answer and drain under the
+// next shift's transforms.
+struct RecoverRows {
+  static constexpr bool kSeg0 = true;  // absent systematic rows are stored (present ones are never marked)
+  cpool_t stores;                      // the payload's row words of the rows to store
+  uint8_t* flag;
+  __device__ __forceinline__ void operator()(const EncTile& t, uint32_t row0, uint32_t mask, const uint32_t (&L)[16],
+                                             const uint32_t (&H)[16], uint32_t lane) const {
+    const uint32_t st = restore_mask16(stores, row0) & mask;
+    compare_rows_masked(t.out, t.shard_len, row0, mask & ~st, L, H, lane, t.ncols, t.full, flag);
+    store_rows_masked(t.out, t.shard_len, row0, st, L, H, lane, t.ncols, t.full, t.nt);
+  }
+};
+
+template <int K>
+__global__ __launch_bounds__(4 * K) __attribute__((amdgpu_waves_per_eu(4))) void k_encode_recover(
+    DevTables T, EncodeArgs a, uint32_t nchunks, uint32_t tiles, const uint32_t* plan, uint8_t* flags) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const uint32_t planw = static_cast<uint32_t>(recover_plan_words(a.n, K));
+#if NP_BOUNDS_CHECK
+  {
+    BoundsSet b = bounds_of_enc(a);  // shards: the received rows, read and written
+    b.lo[kBkRecords] = reinterpret_cast<uint64_t>(plan);
+    b.hi[kBkRecords] = b.lo[kBkRecords] + a.batch * static_cast<uint64_t>(planw) * 4u;
+    b.lo[kBkOut] = reinterpret_cast<uint64_t>(flags);
+    b.hi[kBkOut] = b.lo[kBkOut] + a.batch * static_cast<uint64_t>(a.n);
+    bounds_arm(b);
+  }
+#endif
+  const TileRef tr = tile_of(blockIdx.x, tiles, (a.batch & 7u) == 0);
+  NP_BNOTE(plan + static_cast<size_t>(tr.pb) * planw, 4u * planw, kBkRecords);
+  const cpool_t seg = (cpool_t)(plan) + static_cast<size_t>(tr.pb) * planw;  // scalar loads
+  encode_planned<K>(T, smem, a.n, enc_tile(a, nchunks, tr), seg,
+                    RecoverRows{seg + static_cast<uint32_t>(restore_plan_words(a.n, K)),
+                                flags + static_cast<size_t>(tr.pb) * a.n});
+}
+
+template <int K>
+hipError_t launch_encode_recover_k(const DevTables& T, const EncodeArgs& a, const uint32_t* plan, uint8_t* flags,
+                                   hipStream_t s) {
+  return with_encode_grid(a, one_tile, [&](uint32_t nchunks, uint32_t tiles, uint32_t, uint32_t blocks) {
+    k_encode_recover<K><<<blocks, Geo<K>::kThreads, encode_lds_bytes<K>(), s>>>(T, a, nchunks, tiles, plan, flags);
+  });
+}
+
+}  // namespace
+
+hipError_t launch_encode_recover(const DevTables& T, const EncodeArgs& a, const uint32_t* plan, uint8_t* flags,
+                                 hipStream_t s) {
+  switch (a.k) {
+    case 64: return launch_encode_recover_k<64>(T, a, plan, flags, s);
+    case 128: return launch_encode_recover_k<128>(T, a, plan, flags, s);
+    case 256: return launch_encode_recover_k<256>(T, a, plan, flags, s);
+    default: return hipErrorNotSupported;
+  }
+}
+
 // The dynamic LDS of every kernel of this file (all above the 64 KiB default).
 hipError_t configure_fast_kernels() {
   hipError_t e = hipSuccess;
@@ -2291,6 +2366,10 @@ hipError_t configure_fast_kernels() {
   set(&k_encode_verify_ragged<64>, encode_lds_bytes<64>());
   set(&k_encode_verify_ragged<128>, encode_lds_bytes<128>());
   set(&k_encode_verify_ragged<256>, encode_lds_bytes<256>());
+  // (last: the order of first use is the order of the kernels in the code object)
+  set(&k_encode_recover<64>, encode_lds_bytes<64>());
+  set(&k_encode_recover<128>, encode_lds_bytes<128>());
+  set(&k_encode_recover<256>, encode_lds_bytes<256>());
   return e;
 }
 

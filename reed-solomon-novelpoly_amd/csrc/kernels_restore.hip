@@ -5,6 +5,8 @@
 //    (kernels_fast.hip k_encode_masked) stores and which size-k segments hold
 //    one, as bit words that kernel reads with scalar loads: one pass over the
 //    n present flags per payload instead of one per column tile.
+//    k_verify_plan and k_recover_plan (below) are the same pass for the verify
+//    and for a call that restores and verifies (np_recover_batch_dev).
 //  * k_copy_absent_rows -- every shape without a masked encode: the unchanged
 //    encode writes all rows below wanted_n to a scratch shard buffer, and this
 //    kernel copies the absent rows of the decoded payloads to the caller's
@@ -19,18 +21,24 @@ namespace {
 
 constexpr uint32_t kPlanThreads = 256;
 
-// One workgroup per payload: the plan that marks the rows in [lo, hi) of a
-// decoded payload whose present flag is PRESENT.  A wave takes 64 consecutive
-// rows at a time (one flag byte per lane, a ballot): two row words, and one bit
-// of the segment words (64 rows never straddle a segment: k >= 64).
-template <bool PRESENT>
+// What a plan marks: the absent rows in [lo, hi) (restore), the present ones
+// (verify), or both -- the absent rows below hi and the present ones in
+// [lo, hi) -- with a second array of row words that tells the two apart (recover).
+enum PlanKind { kPlanAbsent, kPlanPresent, kPlanRecover };
+
+// One workgroup per payload: the plan that marks the rows of a decoded payload
+// that KIND names.  A wave takes 64 consecutive rows at a time (one flag byte
+// per lane, a ballot): two row words, and one bit of the segment words (64 rows
+// never straddle a segment: k >= 64).  kPlanRecover: the row words hold the
+// union, and n / 32 further words behind them the rows of the union to store.
+template <PlanKind KIND>
 __device__ __forceinline__ void plan_rows(const uint8_t* __restrict__ present, const uint32_t* __restrict__ status,
                                           uint32_t n, uint32_t k, uint32_t lo, uint32_t hi, size_t batch,
                                           uint32_t* __restrict__ plan) {
   __shared__ uint32_t seg[32];  // n / k <= 1024 segments
   const uint32_t pb = blockIdx.x, tid = threadIdx.x, lane = tid & 63u;
   const uint32_t segw = static_cast<uint32_t>(restore_seg_words(n, k));
-  const size_t words = restore_plan_words(n, k);
+  const size_t words = KIND == kPlanRecover ? recover_plan_words(n, k) : restore_plan_words(n, k);
 #if NP_BOUNDS_CHECK
   {
     BoundsSet b{};
@@ -50,11 +58,23 @@ __device__ __forceinline__ void plan_rows(const uint8_t* __restrict__ present, c
   uint32_t* pl = plan + static_cast<size_t>(pb) * words;
   for (uint32_t v0 = tid - lane; v0 < n; v0 += kPlanThreads) {  // n is a multiple of 64
     const uint32_t v = v0 + lane;
-    const bool mark = ok && v >= lo && v < hi && (*NP_BCHK(pres + v, 1, kBkPresent) != 0) == PRESENT;
+    bool mark, store = false;
+    if constexpr (KIND == kPlanRecover) {
+      const bool here = *NP_BCHK(pres + v, 1, kBkPresent) != 0;
+      store = ok && v < hi && !here;
+      mark = store || (ok && v >= lo && v < hi && here);
+    } else {
+      mark = ok && v >= lo && v < hi && (*NP_BCHK(pres + v, 1, kBkPresent) != 0) == (KIND == kPlanPresent);
+    }
     const uint64_t m = __ballot(mark);
+    const uint64_t ms = KIND == kPlanRecover ? __ballot(store) : 0;
     if (lane == 0) {
       *NP_BCHK(pl + segw + v0 / 32, 8, kBkRecords) = static_cast<uint32_t>(m);
       pl[segw + v0 / 32 + 1] = static_cast<uint32_t>(m >> 32);
+      if constexpr (KIND == kPlanRecover) {
+        *NP_BCHK(pl + segw + n / 32 + v0 / 32, 8, kBkRecords) = static_cast<uint32_t>(ms);
+        pl[segw + n / 32 + v0 / 32 + 1] = static_cast<uint32_t>(ms >> 32);
+      }
       if (m) atomicOr(&seg[(v0 / k) >> 5], 1u << ((v0 / k) & 31u));
     }
   }
@@ -67,7 +87,7 @@ __global__ __launch_bounds__(kPlanThreads) void k_restore_plan(const uint8_t* __
                                                                const uint32_t* __restrict__ status, uint32_t n,
                                                                uint32_t k, uint32_t wanted_n, size_t batch,
                                                                uint32_t* __restrict__ plan) {
-  plan_rows<false>(present, status, n, k, 0, wanted_n, batch, plan);
+  plan_rows<kPlanAbsent>(present, status, n, k, 0, wanted_n, batch, plan);
 }
 
 constexpr uint32_t kCopyWaves = 4;
@@ -170,7 +190,7 @@ __global__ __launch_bounds__(kPlanThreads) void k_verify_plan(const uint8_t* __r
                                                               const uint32_t* __restrict__ status, uint32_t n,
                                                               uint32_t k, uint32_t wanted_n, size_t batch,
                                                               uint32_t* __restrict__ plan) {
-  plan_rows<true>(present, status, n, k, k, wanted_n, batch, plan);
+  plan_rows<kPlanPresent>(present, status, n, k, k, wanted_n, batch, plan);
 }
 
 // One wave per 4 KiB piece of a row in [k, rows) (as k_copy_absent_rows): enc
@@ -296,6 +316,30 @@ hipError_t launch_verify_summary(const uint8_t* flags, const uint32_t* status, u
   if (batch == 0) return hipSuccess;
   if (batch > 0x7fffffffu) return hipErrorInvalidValue;
   k_verify_summary<<<static_cast<uint32_t>(batch), kSummaryThreads, 0, s>>>(flags, status, n, batch, counts);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------ recover ----
+// np_recover_batch_dev with both the restore and the verify requested (engine.cpp
+// launch_recover): one plan for kernels_fast.hip k_encode_recover, which stores
+// the absent rows below wanted_n and compares the present ones in [k, wanted_n)
+// in one pass over the re-encoding.
+namespace {
+
+__global__ __launch_bounds__(kPlanThreads) void k_recover_plan(const uint8_t* __restrict__ present,
+                                                               const uint32_t* __restrict__ status, uint32_t n,
+                                                               uint32_t k, uint32_t wanted_n, size_t batch,
+                                                               uint32_t* __restrict__ plan) {
+  plan_rows<kPlanRecover>(present, status, n, k, k, wanted_n, batch, plan);
+}
+
+}  // namespace
+
+hipError_t launch_recover_plan(const uint8_t* present, const uint32_t* status, uint32_t n, uint32_t k,
+                               uint32_t wanted_n, size_t batch, uint32_t* plan, hipStream_t s) {
+  if (batch == 0) return hipSuccess;
+  if (batch > 0x7fffffffu || k < 64 || n % 64 != 0 || n / k > 1024) return hipErrorInvalidValue;
+  k_recover_plan<<<static_cast<uint32_t>(batch), kPlanThreads, 0, s>>>(present, status, n, k, wanted_n, batch, plan);
   return hipGetLastError();
 }
 

@@ -222,6 +222,22 @@ hipError_t launch_compare_present_rows(const uint8_t* enc, size_t estride, const
 hipError_t launch_verify_summary(const uint8_t* flags, const uint32_t* status, uint32_t n, size_t batch,
                                  uint32_t* counts, hipStream_t s);
 
+// ---- payload, absent rows and verdict from one decode (np_recover_batch_dev) ----
+// The plan of a call that restores and verifies: the restore plan's layout --
+// segment words, then n / 32 row words -- over the union of both purposes (row
+// bit v set when row v below wanted_n of a decoded payload is absent, or present
+// and >= k; these words also drive the encode's segment and butterfly skipping),
+// then n / 32 words with bit v set when row v of the union is stored (absent);
+// the other rows of the union are compared.
+constexpr size_t recover_plan_words(uint32_t n, uint32_t k) { return restore_plan_words(n, k) + n / 32; }
+hipError_t launch_recover_plan(const uint8_t* present, const uint32_t* status, uint32_t n, uint32_t k,
+                               uint32_t wanted_n, size_t batch, uint32_t* plan, hipStream_t s);
+// Where masked_encode_supported: the masked encode's flow; a.shards holds the
+// received rows, of which the plan's absent ones are written and its present
+// ones compared (flags as launch_encode_verify).
+hipError_t launch_encode_recover(const DevTables& T, const EncodeArgs& a, const uint32_t* plan, uint8_t* flags,
+                                 hipStream_t s);
+
 // ---- ragged batches (np_encode_ragged_dev / np_reconstruct_ragged_dev) ----
 // Per-item device record, read with scalar loads by the workgroups of the item:
 // absolute device addresses, the engine adds the caller's bases to the offsets

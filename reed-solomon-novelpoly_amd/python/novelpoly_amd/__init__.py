@@ -84,6 +84,9 @@ def lib() -> C.CDLL:
             "np_rs_restore_shards": (C.c_int, [vp, P, C.POINTER(vp), C.POINTER(_sz), _sz, C.POINTER(vp), _sz]),
             "np_verify_shards_batch_dev": (C.c_int, [vp, P, vp, _sz, _sz, vp, _sz, vp, vp, vp, vp]),
             "np_rs_verify_shards": (C.c_int, [vp, P, C.POINTER(vp), C.POINTER(_sz), _sz, C.POINTER(_sz), vp]),
+            "np_recover_batch_dev": (C.c_int, [vp, P, vp, _sz, _sz, vp, _sz, vp, _sz, C.c_int, vp, vp, vp, vp]),
+            "np_rs_recover": (C.c_int, [vp, P, C.POINTER(vp), C.POINTER(_sz), _sz, vp, _sz, C.POINTER(_sz),
+                                        C.POINTER(vp), _sz, C.POINTER(_sz), vp]),
             "np_encode_ragged_dev": (C.c_int, [vp, P, vp, _sz, vp, _sz, C.POINTER(RaggedItem), _sz, vp]),
             "np_reconstruct_ragged_dev": (C.c_int, [vp, P, vp, _sz, vp, vp, _sz, C.POINTER(RaggedItem), _sz, vp, vp]),
             "np_restore_shards_ragged_dev": (C.c_int, [vp, P, vp, _sz, vp, C.POINTER(RaggedItem), _sz, vp, vp]),
@@ -441,6 +444,31 @@ class ReedSolomon:
                                          None))
         return bad.value == 0
 
+    def recover(self, received: Sequence[Optional[bytes]]):
+        """``(payload, shards, mismatched_rows)`` from one staging and one decode
+        of ``received`` (np_rs_recover): what :meth:`reconstruct`,
+        :meth:`restore_shards` and :meth:`mismatched_shards` return, each
+        exactly.  Raises as :meth:`reconstruct` does."""
+        ptrs, lens, keep = _shard_arrays(received)
+        syms = max([(len(_as_bytes(s)) + 1) // 2 for s in received[: self.n] if s is not None] or [0])
+        sl, cap = 2 * syms, max(1, syms * 2 * self.k)
+        out = C.create_string_buffer(cap)
+        olen = _sz()
+        absent = [i for i in range(self.wanted_n) if i >= len(received) or received[i] is None]
+        bufs = {i: C.create_string_buffer(max(1, sl)) for i in absent}
+        outs = (C.c_void_p * max(1, self.wanted_n))()
+        for i, b in bufs.items():
+            outs[i] = C.cast(b, C.c_void_p)
+        bad = _sz(0)
+        flags = C.create_string_buffer(max(1, self.n))
+        _raise(lib().np_rs_recover(self.ctx.handle, C.byref(self._p), ptrs, lens, len(received), C.cast(out, C.c_void_p),
+                                   cap, C.byref(olen), outs, sl, C.byref(bad), C.cast(flags, C.c_void_p)))
+        shards = [bufs[i].raw[:sl] if i in bufs else WrappedShard(_as_bytes(received[i])).inner
+                  for i in range(self.wanted_n)]
+        rows = [i for i, f in enumerate(flags.raw[: self.n]) if f]
+        assert len(rows) == bad.value
+        return out.raw[: olen.value], shards, rows
+
     def reconstruct_from_systematic(self, chunks: Sequence[bytes]) -> bytes:
         ptrs, lens, keep = _shard_arrays(chunks)
         maxsyms = max([(len(_as_bytes(s)) + 1) // 2 for s in chunks] or [0])
@@ -477,6 +505,13 @@ def verify(received: Sequence[Optional[bytes]], validator_count: int, ctx: Optio
     :func:`reconstruct` derives."""
     params = CodeParams.derive_parameters(validator_count, recoverablity_subset_size(validator_count))
     return params.make_encoder(ctx).verify(received)
+
+
+def recover(received: Sequence[Optional[bytes]], validator_count: int, ctx: Optional[Context] = None):
+    """``(payload, shards, mismatched_rows)`` of the received shards (:meth:`ReedSolomon.recover`),
+    with the code :func:`reconstruct` derives."""
+    params = CodeParams.derive_parameters(validator_count, recoverablity_subset_size(validator_count))
+    return params.make_encoder(ctx).recover(received)
 
 
 # -------------------------------------------------- device-resident batch ----
@@ -542,6 +577,22 @@ def verify_shards_batch_dev(params: CodeParams, d_shards: int, shard_len: int, b
     _raise(lib().np_verify_shards_batch_dev(ctx.handle, C.byref(params._c()), d_shards, shard_len, batch_stride,
                                             d_present, batch, d_bad_rows, d_mismatch or None, d_status or None,
                                             stream or None))
+
+
+def recover_batch_dev(params: CodeParams, d_shards: int, shard_len: int, batch_stride: int, d_present: int,
+                      batch: int, ctx: Optional[Context] = None, stream: int = 0, d_out: int = 0, out_stride: int = 0,
+                      restore: bool = False, d_bad_rows: int = 0, d_mismatch: int = 0, d_status: int = 0) -> None:
+    """The payloads, the absent rows and the verdict from one decode
+    (np_recover_batch_dev): ``d_out`` / ``out_stride`` as
+    :func:`reconstruct_batch_dev2` without locators, ``restore`` as
+    :func:`restore_shards_batch_dev`, ``d_bad_rows`` / ``d_mismatch`` as
+    :func:`verify_shards_batch_dev` -- each output bit for bit that call's, for
+    any received bytes.  At least one of the three is requested; an output that
+    is not requested is never written.  d_status as :func:`reconstruct_batch_dev2`."""
+    ctx = ctx or default_context()
+    _raise(lib().np_recover_batch_dev(ctx.handle, C.byref(params._c()), d_shards or None, shard_len, batch_stride,
+                                      d_present or None, batch, d_out or None, out_stride, 1 if restore else 0,
+                                      d_bad_rows or None, d_mismatch or None, d_status or None, stream or None))
 
 
 NO_ITEM = 0xFFFFFFFF  # block_item of a padding workgroup of ragged_plan
