@@ -319,8 +319,8 @@ int np_recover_batch_dev(np_ctx* ctx, const np_code_params* params, uint8_t* d_s
  * returns and never referenced afterwards. */
 typedef struct np_ragged_item {
   uint64_t payload_off; /* encode: payload at d_payloads + payload_off; reconstruct: output at d_out + payload_off;
-                           restore / verify: ignored, not validated */
-  uint64_t payload_len; /* encode: bytes, > 0.  reconstruct: ignored.  restore / verify: ignored, not validated */
+                           restore / verify: ignored, not validated; recover: as reconstruct with d_out, else ignored */
+  uint64_t payload_len; /* encode: bytes, > 0.  reconstruct: ignored.  restore / verify / recover: ignored, not validated */
   uint64_t shards_off;  /* row v of this item at d_shards + shards_off + v * shard_len */
   uint64_t shard_len;   /* bytes per row, even, > 0; encode: must equal np_shard_len(params, payload_len) */
 } np_ragged_item;
@@ -389,6 +389,45 @@ int np_restore_shards_ragged_dev(np_ctx* ctx, const np_code_params* params, uint
 int np_verify_shards_ragged_dev(np_ctx* ctx, const np_code_params* params, const uint8_t* d_shards, size_t shards_size,
                                 const uint8_t* d_present, const np_ragged_item* items, size_t batch,
                                 uint32_t* d_bad_rows, uint8_t* d_mismatch, np_payload_status* d_status, void* stream);
+/* The payload, the missing shards and the verdict of a ragged batch from one
+ * decode (0.6.0).  Item b is np_recover_batch_dev with batch = 1 on rows
+ * d_shards + shards_off + v * shard_len, presence row b of d_present, output
+ * d_out + payload_off ((shard_len / 2) * 2k bytes written) and entry b of
+ * d_status, d_bad_rows and d_mismatch: each output bit for bit what
+ * np_reconstruct_ragged_dev, np_restore_shards_ragged_dev and
+ * np_verify_shards_ragged_dev give on the same received rows, for any received
+ * bytes.  Everything np_recover_batch_dev documents carries over: any
+ * non-empty subset of {d_out, restore, d_bad_rows (+ d_mismatch)} may be
+ * requested and an output that was not requested is never written; an item
+ * with < k present rows gets NP_ERR_NEED_MORE_SHARDS, UINT32_MAX and an
+ * all-zero map, its d_out bytes and its rows left untouched; the verdict is
+ * that of the received rows (restored rows are absent, compared rows present);
+ * d_bad_rows is counted from the flags.  d_out must not overlap d_shards;
+ * overlap between items' shard ranges or output ranges is undefined when the
+ * restore or the verify is requested.  payload_len is ignored and never
+ * validated.
+ * Validation, all on the host before any launch and in this order: params and
+ * items -- with d_out exactly np_reconstruct_ragged_dev's checks (payload_off
+ * + (shard_len / 2) * 2k against out_size), without it exactly those of the
+ * two calls above (payload_off is then ignored too); a NULL ctx ->
+ * NP_ERR_INVALID_ARGUMENT; nothing requested, or d_mismatch without d_bad_rows
+ * -> NP_ERR_INVALID_ARGUMENT (also at batch == 0); batch == 0 -> NP_OK,
+ * nothing launched; NULL d_shards or d_present -> NP_ERR_INVALID_ARGUMENT.
+ * Asynchronous on `stream`; `items` is not referenced after the call returns.
+ * The payload alone is np_reconstruct_ragged_dev.  k in {64, 128, 256} with
+ * n / k in {2, 4, 8}: with d_out the ragged reconstruct goes straight to the
+ * caller's buffer, which the encode then reads (the context keeps no payloads;
+ * a slice of the batch ends only where the per-item plan words would outgrow
+ * the scratch); without it the slices are those of the two calls above.  A
+ * call that restores and verifies runs one encode that stores the absent rows
+ * and compares the present ones; with one of the two it runs that call's
+ * encode.  Every other shape: maximal runs of consecutive items with equal
+ * shard_len at constant spacings (of the shards, and with d_out of the
+ * outputs) go as one np_recover_batch_dev, anything else one item per call. */
+int np_recover_ragged_dev(np_ctx* ctx, const np_code_params* params, uint8_t* d_shards, size_t shards_size,
+                          const uint8_t* d_present, uint8_t* d_out, size_t out_size, const np_ragged_item* items,
+                          size_t batch, int restore, uint32_t* d_bad_rows, uint8_t* d_mismatch,
+                          np_payload_status* d_status, void* stream);
 /* Pure host code, no device needed: validates `items` exactly as the encode and
  * the reconstruct above do (reconstruct != 0: as np_reconstruct_ragged_dev, payloads_size being
  * its out_size) and returns the launch plan of the direct path: *nblocks

@@ -572,6 +572,48 @@ impl ReedSolomon {
 			stream,
 		))
 	}
+
+	/// np_recover_ragged_dev: from one decode, every item's payload at
+	/// `d_out + payload_off` (`d_out` may be null), its absent rows written
+	/// into `d_shards` (`restore`) and its verdict in `d_bad_rows` /
+	/// `d_mismatch` (both may be null), each as the three calls above give it.
+	/// At least one of the three is requested; `d_status` may be null.
+	/// `d_out` must not overlap `d_shards`.  Asynchronous on `stream`.
+	///
+	/// # Safety
+	/// As `encode_ragged_dev`, for `d_shards`, `d_present`, `d_out`,
+	/// `d_bad_rows`, `d_mismatch` and `d_status`.
+	pub unsafe fn recover_ragged_dev(
+		&self,
+		d_shards: *mut u8,
+		shards_size: usize,
+		d_present: *const u8,
+		d_out: *mut u8,
+		out_size: usize,
+		items: &[sys::np_ragged_item],
+		restore: bool,
+		d_bad_rows: *mut u32,
+		d_mismatch: *mut u8,
+		d_status: *mut sys::np_payload_status,
+		stream: *mut std::ffi::c_void,
+	) -> Result<()> {
+		check(sys::np_recover_ragged_dev(
+			self.ctx.raw,
+			&self.params.raw,
+			d_shards,
+			shards_size,
+			d_present,
+			d_out,
+			out_size,
+			items.as_ptr(),
+			items.len(),
+			restore as c_int,
+			d_bad_rows,
+			d_mismatch,
+			d_status,
+			stream,
+		))
+	}
 }
 
 /// encode.rs:6-11: derives (n, k) from the validator count like the crate.

@@ -229,6 +229,22 @@ extern "C" {
 		d_status: *mut np_payload_status,
 		stream: *mut c_void,
 	) -> c_int;
+	pub fn np_recover_ragged_dev(
+		ctx: *mut np_ctx,
+		params: *const np_code_params,
+		d_shards: *mut u8,
+		shards_size: usize,
+		d_present: *const u8,
+		d_out: *mut u8,
+		out_size: usize,
+		items: *const np_ragged_item,
+		batch: usize,
+		restore: c_int,
+		d_bad_rows: *mut u32,
+		d_mismatch: *mut u8,
+		d_status: *mut np_payload_status,
+		stream: *mut c_void,
+	) -> c_int;
 	pub fn np_ragged_plan(
 		params: *const np_code_params,
 		items: *const np_ragged_item,

@@ -658,7 +658,7 @@ int np_debug_bounds_check(np_ctx* c, uint32_t out[8]) {
   return NP_OK;
 }
 
-const char* np_version(void) { return "novelpoly-mi355x 0.5.0 (gfx950)"; }
+const char* np_version(void) { return "novelpoly-mi355x 0.6.0 (gfx950)"; }
 
 size_t np_recoverability_subset_size(size_t n) { return (n ? (n - 1) / 3 : 0) + 1; }
 
@@ -2072,6 +2072,9 @@ int np_reconstruct_from_systematic_batch_dev(np_ctx* c, const np_code_params* p,
 // np_restore_shards_ragged_dev / np_verify_shards_ragged_dev run
 // the ragged reconstruct into the restore scratch and the ragged masked /
 // verify encode on the same records, in slices of the batch.
+// np_recover_ragged_dev is that flow with the decode optionally
+// into the caller's output buffer and, for a restore with a verify, the ragged
+// recover encode.
 namespace {
 
 constexpr size_t kRaggedTile = 256;  // columns per workgroup (kernels_fast.hip kTile)
@@ -2408,20 +2411,26 @@ size_t ragged_masked_slice_end(const np_ctx* c, const np_code_params* p, const n
 // reconstruct with records {scratch address, (shard_len / 2) * 2k, row 0,
 // shard_len}) and leaves in *sl what the masked launches take.  `own_flags`:
 // bytes per item of a flag map of the call's own (verify without d_mismatch).
+// `both`: the plan of a call that restores and verifies (np::recover_plan_words
+// per item).  With d_out the decode goes to the caller's buffer, item b at
+// d_out + payload_off, and no payload scratch is laid out.
 hipError_t ragged_masked_reconstruct(np_ctx* c, const np_code_params* p, const uint8_t* d_shards, size_t shards_size,
                                      const uint8_t* d_present, const np_ragged_item* items, size_t b0, size_t cnt,
-                                     uint32_t* d_status, size_t own_flags, hipStream_t s, RaggedMaskedSlice* sl) {
+                                     uint32_t* d_status, size_t own_flags, hipStream_t s, RaggedMaskedSlice* sl,
+                                     bool both = false, uint8_t* d_out = nullptr, size_t out_size = 0) {
   const uint32_t n = static_cast<uint32_t>(p->n), k = static_cast<uint32_t>(p->k);
   const size_t own_status = d_status ? 0 : kStatusBytes;
   const size_t stride = np::prefix_stride(n, k);
-  const size_t plan_len = np::restore_plan_words(n, k) * sizeof(uint32_t);
+  const size_t plan_len = (both ? np::recover_plan_words(n, k) : np::restore_plan_words(n, k)) * sizeof(uint32_t);
   std::vector<np::RaggedRec> recs(cnt);
   size_t pay_bytes = 0;
   for (size_t i = 0; i < cnt; ++i) {
     const np_ragged_item& it = items[b0 + i];
+    // (the decoded length, never the item's payload_len: the encode reads the whole padded payload)
     const size_t pay = (it.shard_len / 2) * 2 * p->k;
-    recs[i] = np::RaggedRec{pay_bytes, pay, reinterpret_cast<uint64_t>(d_shards) + it.shards_off, it.shard_len};
-    pay_bytes += align256(pay);
+    recs[i] = np::RaggedRec{d_out ? it.payload_off : pay_bytes, pay,
+                            reinterpret_cast<uint64_t>(d_shards) + it.shards_off, it.shard_len};
+    if (!d_out) pay_bytes += align256(pay);
   }
   sl->cnt = cnt;
   sl->o_plan = pay_bytes;
@@ -2429,7 +2438,7 @@ hipError_t ragged_masked_reconstruct(np_ctx* c, const np_code_params* p, const u
   sl->o_flags = sl->o_status + align256(cnt * own_status);
   hipError_t e = restore_scratch(c, sl->o_flags + align256(cnt * own_flags), s, &sl->scr);
   if (e != hipSuccess) return e;
-  for (np::RaggedRec& rec : recs) rec.data += reinterpret_cast<uint64_t>(sl->scr);
+  for (np::RaggedRec& rec : recs) rec.data += reinterpret_cast<uint64_t>(d_out ? d_out : sl->scr);
   sl->plan = reinterpret_cast<uint32_t*>(sl->scr + sl->o_plan);
   uint8_t* pre = nullptr;
   size_t bytes = 0;
@@ -2445,7 +2454,8 @@ hipError_t ragged_masked_reconstruct(np_ctx* c, const np_code_params* p, const u
   std::vector<uint32_t> bi, bt;
   size_t nblocks = 0;
   ragged_plan(items, b0, cnt, &bi, &bt, &nblocks);
-  sl->r = ragged_args(p, sl->scr, sl->o_plan, d_shards, shards_size);
+  sl->r = d_out ? ragged_args(p, d_out, out_size, d_shards, shards_size)
+                : ragged_args(p, sl->scr, sl->o_plan, d_shards, shards_size);
   sl->r.present = a.present;
   sl->r.prefix = pre;
   sl->r.status = a.status;
@@ -2544,6 +2554,86 @@ hipError_t launch_verify_ragged_all(np_ctx* c, const np_code_params* p, const ui
   return hipSuccess;
 }
 
+// Items [b0, b0 + cnt) of a direct ragged recover with d_out, which keeps no
+// payload in scratch: the slice ends where the plan words, the own status and
+// the own flag rows (`small` bytes per item, three 256-aligned arrays) would
+// pass restore_cap, or the prefix records big_cap; at least one item.
+size_t ragged_recover_slice_end(const np_ctx* c, size_t b0, size_t batch, size_t per_records, size_t small) {
+  const size_t room = c->restore_cap > 3 * 256 ? c->restore_cap - 3 * 256 : 0;
+  return b0 + std::min(batch - b0, std::min(per_records, std::max<size_t>(1, room / small)));
+}
+
+// np_recover_ragged_dev after validation: what launch_restore_ragged_all and
+// launch_verify_ragged_all do, and the payload, from one ragged reconstruct per
+// slice.  With d_out the decode goes straight to the caller's
+// buffer, whose items are then the encode's payloads: no payload scratch.  A
+// direct shape with one request runs that request's plan and ragged encode
+// unchanged; with both, the recover plan and the ragged recover encode.  Every
+// other shape: runs of equally long items at constant spacings through
+// launch_recover.  Caller holds the context lock.
+hipError_t launch_recover_ragged_all(np_ctx* c, const np_code_params* p, uint8_t* d_shards, size_t shards_size,
+                                     const uint8_t* d_present, uint8_t* d_out, size_t out_size,
+                                     const np_ragged_item* items, size_t batch, bool restore, uint32_t* d_bad_rows,
+                                     uint8_t* d_mismatch, uint32_t* d_status, hipStream_t s) {
+  const bool verify = d_bad_rows != nullptr;
+  if (!restore && !verify)  // the payload alone
+    return launch_reconstruct_ragged_all(c, p, d_shards, shards_size, d_present, d_out, out_size, items, batch,
+                                         d_status, s);
+  const uint32_t n = static_cast<uint32_t>(p->n), k = static_cast<uint32_t>(p->k);
+  const uint32_t wanted_n = static_cast<uint32_t>(p->wanted_n);
+  if (np::ragged_masked_supported(n, k)) {
+    // (launch_recover's: the encode runs when a request has a row it can name)
+    const bool both = restore && verify, do_restore = restore && wanted_n, do_verify = verify && wanted_n > k;
+    const size_t own_flags = verify && !d_mismatch ? p->n : 0;
+    const size_t small = (both ? np::recover_plan_words(n, k) : np::restore_plan_words(n, k)) * sizeof(uint32_t) +
+                         (d_status ? 0 : kStatusBytes) + own_flags;
+    const size_t per = std::max<size_t>(1, c->big_cap / np::prefix_stride(n, k));
+    for (size_t b0 = 0; b0 < batch;) {
+      const size_t b1 = d_out ? ragged_recover_slice_end(c, b0, batch, per, small)
+                              : ragged_masked_slice_end(c, p, items, b0, batch, per);
+      RaggedMaskedSlice sl;
+      hipError_t e = ragged_masked_reconstruct(c, p, d_shards, shards_size, d_present, items, b0, b1 - b0, d_status,
+                                               own_flags, s, &sl, both, d_out, out_size);
+      uint8_t* flags = d_mismatch ? d_mismatch + b0 * p->n : sl.scr + sl.o_flags;
+      if (e == hipSuccess && verify) e = HIP(hipMemsetAsync(flags, 0, sl.cnt * p->n, s));
+      if (e == hipSuccess && (do_restore || do_verify)) {
+        if (both) {
+          e = HIP(np::launch_recover_plan(sl.r.present, sl.r.status, n, k, wanted_n, sl.cnt, sl.plan, s));
+          if (e == hipSuccess) e = HIP(np::launch_encode_recover_ragged(c->T, sl.r, sl.plan, flags, s));
+        } else if (restore) {
+          e = HIP(np::launch_restore_plan(sl.r.present, sl.r.status, n, k, wanted_n, sl.cnt, sl.plan, s));
+          if (e == hipSuccess) e = HIP(np::launch_encode_masked_ragged(c->T, sl.r, sl.plan, s));
+        } else {  // (do_verify; the verify encode only reads the rows)
+          e = HIP(np::launch_verify_plan(sl.r.present, sl.r.status, n, k, wanted_n, sl.cnt, sl.plan, s));
+          if (e == hipSuccess) e = HIP(np::launch_encode_verify_ragged(c->T, sl.r, sl.plan, flags, s));
+        }
+      }
+      if (e == hipSuccess && verify)
+        e = HIP(np::launch_verify_summary(flags, sl.r.status, n, sl.cnt, d_bad_rows + b0, s));
+      e = ragged_masked_done(c, s, e);
+      if (e != hipSuccess) return e;
+      b0 = b1;
+    }
+    return hipSuccess;
+  }
+  const uint64_t out_len_k = 2 * static_cast<uint64_t>(p->k);
+  for (size_t b0 = 0; b0 < batch;) {
+    uint64_t ostride = 0, bstride = 0;
+    const size_t b1 = d_out ? ragged_run(items, b0, batch, true, p->n,
+                                         [&](const np_ragged_item& it) { return (it.shard_len / 2) * out_len_k; },
+                                         &ostride, &bstride)
+                            : ragged_shard_run(items, b0, batch, p->n, &bstride);
+    const np_ragged_item& it = items[b0];
+    hipError_t e = launch_recover(c, p, d_shards + it.shards_off, it.shard_len, bstride, d_present + b0 * p->n, b1 - b0,
+                                  d_out ? d_out + it.payload_off : nullptr, ostride, restore,
+                                  d_bad_rows ? d_bad_rows + b0 : nullptr, d_mismatch ? d_mismatch + b0 * p->n : nullptr,
+                                  d_status ? d_status + 2 * b0 : nullptr, s);
+    if (e != hipSuccess) return e;
+    b0 = b1;
+  }
+  return hipSuccess;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2623,6 +2713,26 @@ int np_verify_shards_ragged_dev(np_ctx* c, const np_code_params* p, const uint8_
   (void)hipSetDevice(c->device);
   return dev_err(launch_verify_ragged_all(c, p, d_shards, shards_size, d_present, items, batch, d_bad_rows,
                                           d_mismatch, reinterpret_cast<uint32_t*>(d_status), pick(c, stream)));
+}
+
+// (Validates the items before the context, as the two calls above; the output
+// extent only when an output is given.)
+int np_recover_ragged_dev(np_ctx* c, const np_code_params* p, uint8_t* d_shards, size_t shards_size,
+                          const uint8_t* d_present, uint8_t* d_out, size_t out_size, const np_ragged_item* items,
+                          size_t batch, int restore, uint32_t* d_bad_rows, uint8_t* d_mismatch,
+                          np_payload_status* d_status, void* stream) {
+  int st = d_out ? ragged_validate(p, items, batch, true, out_size, shards_size)
+                 : ragged_masked_validate(p, items, batch, shards_size);
+  if (st) return st;
+  if (!c) return fail(NP_ERR_INVALID_ARGUMENT);
+  if ((!d_out && !restore && !d_bad_rows) || (d_mismatch && !d_bad_rows)) return fail(NP_ERR_INVALID_ARGUMENT);
+  if (batch == 0) return NP_OK;
+  if (!d_shards || !d_present) return fail(NP_ERR_INVALID_ARGUMENT);
+  std::lock_guard<std::mutex> g(c->mu);  // context scratch
+  (void)hipSetDevice(c->device);
+  return dev_err(launch_recover_ragged_all(c, p, d_shards, shards_size, d_present, d_out, out_size, items, batch,
+                                           restore != 0, d_bad_rows, d_mismatch,
+                                           reinterpret_cast<uint32_t*>(d_status), pick(c, stream)));
 }
 
 // ------------------------------------------------------------ multi-GPU ----

@@ -2314,6 +2314,41 @@ hipError_t launch_encode_recover(const DevTables& T, const EncodeArgs& a, const 
   }
 }
 
+// ------------------------------------------------ ragged recover encode ----
+// np_recover_ragged_dev with the restore and the verify requested:
+// k_encode_recover's flow with the ragged head.  The item's record names its
+// decoded payload (in the context scratch, or in the caller's output buffer at
+// any byte address) and its shard rows; the plan words (k_recover_plan) and the
+// flag row stay per item at their fixed strides.
+// (Last in the file and in configure_fast_kernels, as k_encode_recover was.)
+namespace {
+
+// One workgroup: one 256-column tile of one item, the absent rows of the item's
+// plan stored into its shard rows and the present ones compared with them.
+template <int K>
+__global__ __launch_bounds__(4 * K) __attribute__((amdgpu_waves_per_eu(4))) void k_encode_recover_ragged(
+    DevTables T, RaggedArgs r, const uint32_t* plan, uint8_t* flags) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const uint32_t planw = static_cast<uint32_t>(recover_plan_words(r.n, K));
+#if NP_BOUNDS_CHECK
+  {
+    BoundsSet b = bounds_of_ragged_masked(r, T, plan, flags);  // shards: the received rows, read and written
+    b.hi[kBkRecords] = b.lo[kBkRecords] + static_cast<uint64_t>(r.nitems) * planw * 4u;
+    bounds_arm(b);
+  }
+#endif
+  const RaggedHead h = ragged_head(r);
+  if (h.item == kRaggedNoItem) return;  // padding of the plan
+  // (plan_of steps by the restore plan's words; this plan is longer)
+  NP_BNOTE(plan + static_cast<size_t>(h.item) * planw, 4u * planw, kBkRecords);
+  const cpool_t seg = (cpool_t)(plan) + static_cast<size_t>(h.item) * planw;  // scalar loads
+  encode_planned<K>(T, smem, r.n, enc_tile(h), seg,
+                    RecoverRows{seg + static_cast<uint32_t>(restore_plan_words(r.n, K)),
+                                flags + static_cast<size_t>(h.item) * r.n});
+}
+
+}  // namespace
+
 // The dynamic LDS of every kernel of this file (all above the 64 KiB default).
 hipError_t configure_fast_kernels() {
   hipError_t e = hipSuccess;
@@ -2370,6 +2405,9 @@ hipError_t configure_fast_kernels() {
   set(&k_encode_recover<64>, encode_lds_bytes<64>());
   set(&k_encode_recover<128>, encode_lds_bytes<128>());
   set(&k_encode_recover<256>, encode_lds_bytes<256>());
+  set(&k_encode_recover_ragged<64>, encode_lds_bytes<64>());
+  set(&k_encode_recover_ragged<128>, encode_lds_bytes<128>());
+  set(&k_encode_recover_ragged<256>, encode_lds_bytes<256>());
   return e;
 }
 
@@ -2400,6 +2438,25 @@ hipError_t launch_encode_verify_ragged(const DevTables& T, const RaggedArgs& r, 
       break;
     case 256:
       k_encode_verify_ragged<256><<<r.nblocks, Geo<256>::kThreads, encode_lds_bytes<256>(), s>>>(T, r, plan, flags);
+      break;
+    default: return hipErrorNotSupported;
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_encode_recover_ragged(const DevTables& T, const RaggedArgs& r, const uint32_t* plan, uint8_t* flags,
+                                        hipStream_t s) {
+  if (r.nblocks == 0) return hipSuccess;
+  if (r.nblocks > 0x7fffffffu) return hipErrorInvalidValue;
+  switch (r.k) {
+    case 64:
+      k_encode_recover_ragged<64><<<r.nblocks, Geo<64>::kThreads, encode_lds_bytes<64>(), s>>>(T, r, plan, flags);
+      break;
+    case 128:
+      k_encode_recover_ragged<128><<<r.nblocks, Geo<128>::kThreads, encode_lds_bytes<128>(), s>>>(T, r, plan, flags);
+      break;
+    case 256:
+      k_encode_recover_ragged<256><<<r.nblocks, Geo<256>::kThreads, encode_lds_bytes<256>(), s>>>(T, r, plan, flags);
       break;
     default: return hipErrorNotSupported;
   }

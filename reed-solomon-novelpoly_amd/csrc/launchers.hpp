@@ -286,4 +286,12 @@ bool ragged_masked_supported(uint32_t n, uint32_t k);
 hipError_t launch_encode_masked_ragged(const DevTables& T, const RaggedArgs& r, const uint32_t* plan, hipStream_t s);
 hipError_t launch_encode_verify_ragged(const DevTables& T, const RaggedArgs& r, const uint32_t* plan, uint8_t* flags,
                                        hipStream_t s);
+
+// ---- ragged recover (np_recover_ragged_dev with the restore and the verify) ----
+// k_encode_recover's flow per block-table entry, on the records of the masked
+// launches above (r.data_base / r.data_size: the payload scratch, or the
+// caller's output buffer that took the decode).  plan: recover_plan_words(n, k)
+// words per item (launch_recover_plan); flags: n bytes per item.
+hipError_t launch_encode_recover_ragged(const DevTables& T, const RaggedArgs& r, const uint32_t* plan, uint8_t* flags,
+                                        hipStream_t s);
 }  // namespace np

@@ -91,6 +91,8 @@ def lib() -> C.CDLL:
             "np_reconstruct_ragged_dev": (C.c_int, [vp, P, vp, _sz, vp, vp, _sz, C.POINTER(RaggedItem), _sz, vp, vp]),
             "np_restore_shards_ragged_dev": (C.c_int, [vp, P, vp, _sz, vp, C.POINTER(RaggedItem), _sz, vp, vp]),
             "np_verify_shards_ragged_dev": (C.c_int, [vp, P, vp, _sz, vp, C.POINTER(RaggedItem), _sz, vp, vp, vp, vp]),
+            "np_recover_ragged_dev": (C.c_int, [vp, P, vp, _sz, vp, vp, _sz, C.POINTER(RaggedItem), _sz, C.c_int, vp,
+                                                vp, vp, vp]),
             "np_ragged_plan": (C.c_int, [P, C.POINTER(RaggedItem), _sz, C.c_int, _sz, _sz, C.POINTER(C.c_uint32),
                                          C.POINTER(C.c_uint32), _sz, C.POINTER(_sz)]),
             "np_error_locator_dev": (C.c_int, [vp, _sz, vp, _sz, vp, vp]),
@@ -667,6 +669,24 @@ def verify_shards_ragged_dev(params: CodeParams, d_shards: int, shards_size: int
     _raise(lib().np_verify_shards_ragged_dev(ctx.handle, C.byref(params._c()), d_shards or None, shards_size,
                                              d_present or None, _ragged_array(items), len(items), d_bad_rows or None,
                                              d_mismatch or None, d_status or None, stream or None))
+
+
+def recover_ragged_dev(params: CodeParams, d_shards: int, shards_size: int, d_present: int, items, d_out: int = 0,
+                       out_size: int = 0, restore: bool = False, d_bad_rows: int = 0, d_mismatch: int = 0,
+                       d_status: int = 0, ctx: Optional[Context] = None, stream: int = 0) -> None:
+    """:func:`recover_batch_dev` on a ragged buffer (np_recover_ragged_dev):
+    from one decode, item b's payload at ``d_out + payload_off`` as
+    :func:`reconstruct_ragged_dev`, its absent rows as
+    :func:`restore_shards_ragged_dev` (``restore``) and its verdict as
+    :func:`verify_shards_ragged_dev` (``d_bad_rows`` / ``d_mismatch``) -- each
+    output bit for bit that call's.  At least one of the three is requested; an
+    output that is not requested is never written.  Without ``d_out``,
+    ``payload_off`` is ignored."""
+    ctx = ctx or default_context()
+    _raise(lib().np_recover_ragged_dev(ctx.handle, C.byref(params._c()), d_shards or None, shards_size,
+                                       d_present or None, d_out or None, out_size, _ragged_array(items), len(items),
+                                       1 if restore else 0, d_bad_rows or None, d_mismatch or None, d_status or None,
+                                       stream or None))
 
 
 def ragged_plan(params: CodeParams, items, reconstruct: bool, payloads_size: int, shards_size: int):
