@@ -59,15 +59,12 @@ class Expected:
     pass
 
 
-@functools.lru_cache(maxsize=None)
-def _recover_case(oracle, nw, kw, batch, rot):
-    """The staged buffers and the oracle's answers, computed once (read only)."""
-    c = _mcase(oracle, nw, kw, batch)
+def expected_items(oracle, c, names, per_item):
+    """The staged buffers of the items `per_item` [(rows, present)] of case `c`
+    and the oracle's answer for each item alone."""
     n, k, wn = c.n, c.k, c.wn
-    rng = np.random.default_rng(1000 * nw + kw + 19 * batch + rot)
     e = Expected()
-    e.names = [PATTERNS[(i + rot) % len(PATTERNS)] for i in range(len(c.items))]
-    per_item = [_pattern(c, rng, i, *e.names[i]) for i in range(len(c.items))]
+    e.names = names
     e.before, e.pres = _stage(c, per_item)
     e.restored = e.before.copy()  # every byte but the restored rows stays as it was
     e.out = np.full(c.psize, GUARD, np.uint8)
@@ -77,7 +74,7 @@ def _recover_case(oracle, nw, kw, batch, rot):
         po, _, _, sl = c.items[i]
         recv = [rows[v].tobytes() if pr[v] else None for v in range(n)]
         st, pay = oracle.reconstruct(recv, n, k)
-        assert (st != 0) == (e.names[i][1] == "k-1"), e.names[i]
+        assert (st != 0) == (int(pr.sum()) < k), names[i]
         if st:
             assert st == npa.NeedMoreShards.code
             counts.append(UNDECODABLE)
@@ -86,7 +83,7 @@ def _recover_case(oracle, nw, kw, batch, rot):
         assert len(pay) == (sl // 2) * 2 * k
         e.out[po:po + len(pay)] = np.frombuffer(pay, np.uint8)
         st, enc = oracle.encode(pay, n, k, wn)
-        assert st == 0 and len(enc) == wn and len(enc[0]) == sl
+        assert st == 0 and len(enc) == wn and all(len(row) == sl for row in enc)
         view = c.item_rows(e.restored, i)
         for v in range(wn):
             if not pr[v]:
@@ -96,6 +93,18 @@ def _recover_case(oracle, nw, kw, batch, rot):
         counts.append(int(e.flags[i].sum()))
         e.status.append((0, int(pr.sum())))
     e.counts = np.asarray(counts, np.uint32)
+    return e
+
+
+@functools.lru_cache(maxsize=None)
+def _recover_case(oracle, nw, kw, batch, rot):
+    """The staged buffers and the oracle's answers, computed once (read only)."""
+    c = _mcase(oracle, nw, kw, batch)
+    rng = np.random.default_rng(1000 * nw + kw + 19 * batch + rot)
+    names = [PATTERNS[(i + rot) % len(PATTERNS)] for i in range(len(c.items))]
+    e = expected_items(oracle, c, names, [_pattern(c, rng, i, *names[i]) for i in range(len(c.items))])
+    for name, (st, _) in zip(names, e.status):
+        assert (st != 0) == (name[1] == "k-1"), name
     for a in (e.before, e.pres, e.restored, e.out, e.flags):
         a.setflags(write=False)
     return e

@@ -22,7 +22,7 @@ import pytest
 
 import novelpoly_amd as npa
 from test_gpu_restore import expected_rows
-from test_gpu_verify import _codeword, _flip, expected_case
+from test_gpu_verify import SlicesCase, _codeword, _flip, expected_case
 
 pytestmark = pytest.mark.gpu
 
@@ -128,18 +128,22 @@ def expected_recover(oracle, p, sl, pats):
     return rows, case, pays
 
 
-def run_recover(gpu, p, sl, pats, expected, offset=0, slack=64, combos=COMBOS, label=""):
+def run_recover(gpu, p, sl, pats, expected, offset=0, slack=64, combos=COMBOS, label="", out_offset=0,
+                out_slack=OUT_SLACK, variants=None):
     """One batch of `pats` under `p` against `expected` (expected_recover), once
     per request combination, with and without d_status and d_mismatch: every
     byte of the shard buffer, of d_out, of the counts and the map and their
-    guards, and the statuses."""
+    guards, and the statuses.  d_out sits `out_offset` bytes behind its 64 guard
+    bytes with out_stride = payload length + `out_slack`; `variants`: the calls
+    as [((d_out, restore, verify), d_status given, d_mismatch given)] in place
+    of every one of `combos`."""
     import torch
 
     exp_rows, (want_flags, want_counts, status), pays = expected
     n, k = p.n(), p.k()
     batch, stride = len(pats), n * sl + slack
     pay_len = (sl // 2) * 2 * k
-    ostride = pay_len + OUT_SLACK
+    ostride = pay_len + out_slack
     before = np.full(offset + batch * stride + 64, FILL, np.uint8)
     for b, (name, rows, pr) in enumerate(pats):
         view = before[offset + b * stride: offset + b * stride + n * sl].reshape(n, sl)
@@ -157,17 +161,19 @@ def run_recover(gpu, p, sl, pats, expected, offset=0, slack=64, combos=COMBOS, l
     dpres = _dev(np.stack([pr for _, _, pr in pats]))
     dbefore = _dev(before)
     s = torch.cuda.current_stream().cuda_stream
-    for (with_out, restore, verify), with_status, with_map in itertools.product(combos, (True, False), (True, False)):
-        if with_map and not verify:
-            continue
+    if variants is None:
+        variants = [v for v in itertools.product(combos, (True, False), (True, False)) if v[0][2] or not v[2]]
+    for (with_out, restore, verify), with_status, with_map in variants:
+        assert verify or not with_map
         tag = f"{label} out {with_out}, restore {restore}, verify {verify}, status {with_status}, map {with_map}"
         buf = dbefore.clone()
         st_d = torch.full((batch, 2), -1, dtype=torch.int32, device="cuda")
         cnt_d = torch.full((64 + 4 * batch + 64,), GUARD, dtype=torch.uint8, device="cuda")
         map_d = torch.full((64 + batch * n + 64,), GUARD, dtype=torch.uint8, device="cuda")
-        out_d = torch.full((64 + batch * ostride + 64,), GUARD, dtype=torch.uint8, device="cuda")
+        out_d = torch.full((64 + out_offset + batch * ostride + 64,), GUARD, dtype=torch.uint8, device="cuda")
         npa.recover_batch_dev(p, buf.data_ptr() + offset, sl, stride, dpres.data_ptr(), batch, ctx=gpu, stream=s,
-                              d_out=out_d.data_ptr() + 64 if with_out else 0, out_stride=ostride if with_out else 0,
+                              d_out=out_d.data_ptr() + 64 + out_offset if with_out else 0,
+                              out_stride=ostride if with_out else 0,
                               restore=restore, d_bad_rows=cnt_d.data_ptr() + 64 if verify else 0,
                               d_mismatch=map_d.data_ptr() + 64 if with_map else 0,
                               d_status=st_d.data_ptr() if with_status else 0)
@@ -183,9 +189,9 @@ def run_recover(gpu, p, sl, pats, expected, offset=0, slack=64, combos=COMBOS, l
                                      f"(absent: {[v for v in rows_bad if v < n and not pr[v]]})")
         assert np.array_equal(got[:offset], want[:offset]) and np.array_equal(got[-64:], want[-64:]), tag
         # the payloads
-        assert (out[:64] == GUARD).all() and (out[-64:] == GUARD).all(), tag
+        assert (out[:64 + out_offset] == GUARD).all() and (out[-64:] == GUARD).all(), tag
         if with_out:
-            o = out[64:-64].reshape(batch, ostride)
+            o = out[64 + out_offset:-64].reshape(batch, ostride)
             for b, (name, _, _) in enumerate(pats):
                 assert np.array_equal(o[b], want_out[b]), (tag, b, name, int(np.flatnonzero(o[b] != want_out[b])[0]))
         else:
@@ -354,3 +360,42 @@ def test_recover_host_single(gpu, oracle, nw, kw):
     with pytest.raises(npa.NeedMoreShards) as ei:
         rs.recover(short)
     assert ei.value == npa.NeedMoreShards(k - 1, k, n)
+
+
+@pytest.mark.parametrize("nw,kw,batch,scratch", [(256, 86, 1100, 1 << 20), (1024, 512, 520, 2 << 20)])
+def test_recover_slices(gpu, nw, kw, batch, scratch):
+    """Payloads of 1 MiB.  (256, 86), direct: 1100 of them are two uneven slices
+    of the 1 GiB payload scratch of an MI355X, as test_restore_slices.
+    (1024, 512): scratch rows of 2 MiB per payload, so 520 of them are slices of
+    512 and 8.  Restore and verify without d_out run per slice at
+    d_shards + b0 * batch_stride, with the map and the status of the caller at
+    their slice offsets or the call's own; with d_out the direct shape is one
+    slice and the other is sliced as before.  SlicesCase works the slice length
+    out from the device's memory as the context does, and asserts that the batch
+    is more than one slice and that every slice holds every payload class.
+    Compared on the device."""
+    import torch
+
+    c = SlicesCase(gpu, nw, kw, batch, scratch)
+    s = torch.cuda.current_stream().cuda_stream
+    for with_out, given in ((False, True), (False, False), (True, True)):
+        tag = f"out {with_out}, map and status {given}"
+        cnt = torch.full((batch,), 7, dtype=torch.int32, device="cuda")
+        mp = torch.full((batch, c.n), GUARD, dtype=torch.uint8, device="cuda")
+        st = torch.full((batch, 2), -1, dtype=torch.int32, device="cuda")
+        out = torch.full((batch, c.plen), GUARD, dtype=torch.uint8, device="cuda") if with_out else None
+        npa.recover_batch_dev(c.p, c.work.data_ptr(), c.sl, c.n * c.sl, c.pres.data_ptr(), batch, ctx=gpu, stream=s,
+                              d_out=out.data_ptr() if with_out else 0, out_stride=c.plen if with_out else 0,
+                              restore=True, d_bad_rows=cnt.data_ptr(), d_mismatch=mp.data_ptr() if given else 0,
+                              d_status=st.data_ptr() if given else 0)
+        torch.cuda.synchronize()
+        assert torch.equal(cnt, c.counts), (tag, (cnt != c.counts).nonzero()[:8].tolist())
+        assert torch.equal(c.work, c.want), (tag, (c.work != c.want).any(dim=2).nonzero()[:8].tolist())
+        if given:
+            assert torch.equal(mp, c.flags) and torch.equal(st, c.status), tag
+        else:
+            assert bool((mp == GUARD).all()) and bool((st == -1).all()), tag
+        if with_out:
+            assert torch.equal(out[~c.c], c.pay[~c.c]) and bool((out[c.c] == GUARD).all()), tag
+        del out
+        c.blank()

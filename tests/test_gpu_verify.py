@@ -332,3 +332,104 @@ def test_verify_host_single(gpu, oracle, nw, kw):
         with pytest.raises(npa.NeedMoreShards) as ei:
             call(short)
         assert ei.value == npa.NeedMoreShards(k - 1, k, n)
+
+
+def slice_len(scratch):
+    """Payloads per slice of a uniform restore / verify / recover call that keeps
+    `scratch` bytes per payload in context scratch (masked_shape in engine.cpp):
+    an eighth of the context's scratch cap, which is a 32nd of the device's
+    memory within 2 .. 8 GiB, in multiples of 8 payloads.  1 GiB of an MI355X."""
+    import torch
+
+    cap = min(8 << 30, max(2 << 30, torch.cuda.get_device_properties(0).total_memory // 32)) // 8
+    per = cap // scratch
+    return per & ~7 if per >= 8 else max(1, per)
+
+
+class SlicesCase:
+    """A batch too large for one scratch slice, generated, blanked and compared
+    on the device (no oracle: the truth is the encode of the payloads).  `work`
+    is encode(pay) with the absent rows set to FILL, `want` what a restore
+    leaves.  Three payload classes, each in every slice:
+      A (even b): every systematic row present, (n - k) / 2 parity rows absent,
+        one byte altered in one present parity row: exactly that row mismatches;
+      B (odd b): (n - k) / 2 absences anywhere, nothing altered: no mismatch;
+      C (b = 96 mod 97, and the last b): k - 1 present rows: NeedMoreShards,
+        nothing touched.
+    `scratch` is what the call keeps in context scratch per payload, in bytes:
+    the decoded payload (verify, and restore or recover without d_out), or the
+    n shard rows where the row-masked encodes do not serve (n, k).  The case
+    asserts that the batch is then more than one slice on this device, and that
+    every slice holds all three classes."""
+
+    def __init__(self, gpu, nw, kw, batch, scratch, plen=1 << 20):
+        import torch
+
+        p = npa.CodeParams.derive_parameters(nw, kw)
+        n, k = p.n(), p.k()
+        sl = p.make_encoder(gpu).shard_len(plen)
+        assert (sl // 2) * 2 * k == plen and p.wanted_n == n
+        s = torch.cuda.current_stream().cuda_stream
+        gen = torch.Generator(device="cuda").manual_seed(7 + n + k)
+        self.p, self.n, self.k, self.sl, self.batch, self.plen = p, n, k, sl, batch, plen
+        self.pay = torch.randint(0, 256, (batch, plen), dtype=torch.uint8, device="cuda", generator=gen)
+        want = torch.empty((batch, n, sl), dtype=torch.uint8, device="cuda")
+        npa.encode_batch_dev(p, self.pay.data_ptr(), plen, plen, batch, want.data_ptr(), n * sl, ctx=gpu, stream=s)
+        b = torch.arange(batch, device="cuda")
+        self.c = (b % 97 == 96) | (b == batch - 1)
+        self.a = (b % 2 == 0) & ~self.c
+        gone = (n - k) // 2
+        rnd = torch.rand((batch, n), device="cuda", generator=gen)
+        rnd[:, :k] += 2.0 * self.a[:, None]  # A: the parity rows come first in the order
+        order = rnd.argsort(dim=1)
+        ones = torch.ones((batch, n), dtype=torch.uint8, device="cuda")
+        self.pres = torch.where(self.c[:, None], ones.scatter(1, order[:, : n - k + 1], 0),
+                                ones.scatter(1, order[:, :gone], 0))
+        ia = self.a.nonzero().squeeze(1)
+        hit = order[ia, gone]  # A: the first parity row that stays present
+        col = torch.randint(0, sl, (ia.numel(),), device="cuda", generator=gen)
+        want[ia, hit, col] ^= 0x40
+        self.flags = torch.zeros((batch, n), dtype=torch.uint8, device="cuda")
+        self.flags[ia, hit] = 1
+        self.counts = torch.where(self.c, -1, self.a.to(torch.int32)).to(torch.int32)  # -1: UINT32_MAX
+        self.status = torch.stack([torch.where(self.c, npa.NeedMoreShards.code, 0),
+                                   torch.where(self.c, k - 1, n - gone)], dim=1).to(torch.int32)
+        self.work = want.clone()
+        self.blank()
+        want[self.c] = self.work[self.c]
+        self.want = want
+        torch.cuda.synchronize()
+        assert bool((hit >= k).all()) and bool((self.pres[ia, hit] == 1).all())
+        assert bool((self.pres.sum(dim=1) == self.status[:, 1]).all())
+        self.per = slice_len(scratch)
+        assert self.per < batch, f"one slice of {self.per} payloads takes the whole batch of {batch}"
+        for b0 in range(0, batch, self.per):
+            for name, cls in (("A", self.a), ("B", ~self.a & ~self.c), ("C", self.c)):
+                assert bool(cls[b0 : b0 + self.per].any()), f"no payload of class {name} in the slice at {b0}"
+
+    def blank(self):
+        """Absent rows back to FILL: `work` as it was before a restore."""
+        self.work[self.pres == 0] = FILL
+
+
+def test_verify_slices(gpu):
+    """1100 payloads of 1 MiB at n256 k64 (two uneven slices of the payload
+    scratch on an MI355X, as test_restore_slices): counts, the map at
+    d_mismatch + b0 * n or the call's own per slice, and the statuses.
+    SlicesCase asserts that the batch is sliced and every class in every slice."""
+    import torch
+
+    c = SlicesCase(gpu, 256, 86, 1100, scratch=1 << 20)
+    s = torch.cuda.current_stream().cuda_stream
+    before = c.work.clone()
+    for with_map in (True, False):
+        cnt = torch.full((c.batch,), 7, dtype=torch.int32, device="cuda")
+        mp = torch.full((c.batch, c.n), GUARD, dtype=torch.uint8, device="cuda")
+        st = torch.full((c.batch, 2), -1, dtype=torch.int32, device="cuda")
+        npa.verify_shards_batch_dev(c.p, c.work.data_ptr(), c.sl, c.n * c.sl, c.pres.data_ptr(), c.batch,
+                                    cnt.data_ptr(), ctx=gpu, stream=s, d_mismatch=mp.data_ptr() if with_map else 0,
+                                    d_status=st.data_ptr())
+        torch.cuda.synchronize()
+        assert torch.equal(cnt, c.counts), (with_map, (cnt != c.counts).nonzero()[:8].tolist())
+        assert torch.equal(mp, c.flags) if with_map else bool((mp == GUARD).all()), with_map
+        assert torch.equal(st, c.status) and torch.equal(c.work, before), with_map
