@@ -468,6 +468,45 @@ int np_encode_batch_host(np_ctx* ctx, const np_code_params* params, const uint8_
 int np_reconstruct_batch_host(np_ctx* ctx, const np_code_params* params, const uint8_t* shards, size_t shard_len,
                               size_t batch_stride, const uint8_t* present, size_t batch, uint8_t* out,
                               size_t out_stride);
+/* np_recover_batch_dev for a batch in HOST memory, pipelined like the two calls
+ * above: per payload the decoded payload (out, may be NULL), the missing shards
+ * (restore != 0) and the verdict (bad_rows, may be NULL; mismatch, may be NULL)
+ * from one decode.  All pointers are host memory, laid out as in
+ * np_recover_batch_dev: row v of payload b at shards + b*batch_stride +
+ * v*shard_len, present batch x n bytes, out spaced at out_stride, bad_rows batch
+ * entries, mismatch batch x n bytes, status (may be NULL) batch entries.
+ * Each requested output is, bit for bit, what np_recover_batch_dev gives on the
+ * same bytes, for any received bytes.  An output that was not requested is never
+ * written.  In `shards` only the absent rows below wanted_n of payloads that
+ * decode are written (restore != 0); no other byte of it changes -- present
+ * rows, rows >= wanted_n, the gap up to batch_stride -- and absent rows are
+ * never read.  The call returns when every output is in host memory.
+ * Only what the answer needs crosses PCIe: in, the present rows the kernels
+ * read (the k systematic rows when no verdict is asked for and every payload has
+ * them all; every present row otherwise); out, the payloads, the restored rows
+ * -- packed on the device, so present rows never come back -- and the counts,
+ * map and statuses that were requested.
+ * A payload with < k present rows: with status != NULL it gets
+ * {NP_ERR_NEED_MORE_SHARDS, have}, UINT32_MAX in bad_rows and an all-zero map
+ * row, its out bytes and rows stay untouched, none of its rows crosses PCIe, and
+ * the call goes on and returns NP_OK.  With status == NULL the call fails up
+ * front with NP_ERR_NEED_MORE_SHARDS, detail {have, k, n} of the first such
+ * payload, as np_reconstruct_batch_host does, and nothing is written.
+ * Validation, before the context is touched, in this order: NULL ctx
+ * (NP_ERR_INVALID_ARGUMENT); the code parameters; a zero or odd shard_len
+ * (NP_ERR_EMPTY_SHARD); NULL shards or present, or batch_stride < n*shard_len
+ * (NP_ERR_INVALID_ARGUMENT); nothing requested, mismatch without bad_rows, or
+ * out with out_stride < (shard_len/2)*2k (NP_ERR_INVALID_ARGUMENT); batch == 0
+ * returns NP_OK; then the mask check above.
+ * Host memory: `shards` always goes through the context's pinned staging, also
+ * when the caller pinned it; this call never registers caller memory, and
+ * NP_PAGEABLE=pin is not honoured here.  An `out` the caller pinned is written
+ * by DMA.  NP_PIPE_SLOTS and NP_PIPE_SB (payloads per sub-batch) are read per
+ * call as in np_reconstruct_batch_host.  There are no separate restore-only or
+ * verify-only host batch entries: they are this call with one request. */
+int np_recover_batch_host(np_ctx* ctx, const np_code_params* params, uint8_t* shards, size_t shard_len,
+                          size_t batch_stride, const uint8_t* present, size_t batch, uint8_t* out, size_t out_stride,
+                          int restore, uint32_t* bad_rows, uint8_t* mismatch, np_payload_status* status);
 
 /* ---- multi-GPU: one batch over several devices ------------------------------
  * payloads are independent, so `batch` splits into contiguous
@@ -497,6 +536,24 @@ int np_encode_batch_host_multi(np_ctx* const* ctxs, size_t nctx, const np_code_p
 int np_reconstruct_batch_host_multi(np_ctx* const* ctxs, size_t nctx, const np_code_params* params,
                                     const uint8_t* shards, size_t shard_len, size_t batch_stride,
                                     const uint8_t* present, size_t batch, uint8_t* out, size_t out_stride);
+/* np_recover_batch_dev over several contexts: d_shards[i] / d_present[i] and,
+ * where requested, d_out[i] / d_bad_rows[i] / d_mismatch[i] / d_status[i] are
+ * device i's buffers holding its range.  A NULL array (d_out, d_bad_rows,
+ * d_mismatch, d_status) means that output is not requested; validation per
+ * range as np_recover_batch_dev.  The code parameters are checked first, also
+ * at batch == 0. */
+int np_recover_batch_multi(np_ctx* const* ctxs, size_t nctx, const np_code_params* params, uint8_t* const* d_shards,
+                           size_t shard_len, size_t batch_stride, const uint8_t* const* d_present, size_t batch,
+                           uint8_t* const* d_out, size_t out_stride, int restore, uint32_t* const* d_bad_rows,
+                           uint8_t* const* d_mismatch, np_payload_status* const* d_status);
+/* np_recover_batch_host over several contexts: each worker takes its range of
+ * the one buffer set (no caller memory is registered, so neighbouring ranges
+ * share nothing).  With status == NULL the mask check runs once over the whole
+ * batch before any worker starts. */
+int np_recover_batch_host_multi(np_ctx* const* ctxs, size_t nctx, const np_code_params* params, uint8_t* shards,
+                                size_t shard_len, size_t batch_stride, const uint8_t* present, size_t batch,
+                                uint8_t* out, size_t out_stride, int restore, uint32_t* bad_rows, uint8_t* mismatch,
+                                np_payload_status* status);
 
 /* ---- low-level parity hooks (device pointers, `cols` independent columns) ----
  * data layout: column c, position i at d_data[c*size + i] (uint16, plain values). */

@@ -422,6 +422,66 @@ impl ReedSolomon {
 		Ok(out)
 	}
 
+	/// The payload, the missing shards and the verdict of `batch` payloads'
+	/// received rows from one decode each (`np_recover_batch_host`), layouts as
+	/// `reconstruct_batch` (`shards.len() == batch * n * shard_len`).
+	/// `out`: the payloads, `shard_len / 2 * 2 * k` bytes each; `restore`: the
+	/// absent rows below `wanted_n` are written into `shards` and no other byte
+	/// of it; `bad_rows`: per payload the number of present rows that differ
+	/// from `encode(reconstruct(received))` (`u32::MAX` when it does not
+	/// decode), `mismatch` (`batch * n`, with `bad_rows` only): which rows.
+	/// With `status` a payload with fewer than k present rows is reported there
+	/// (`NP_ERR_NEED_MORE_SHARDS`, its present count) and left untouched;
+	/// without it such a payload fails the call with NeedMoreShards before
+	/// anything is written.  At least one of `out`, `restore`, `bad_rows`.
+	#[allow(clippy::too_many_arguments)]
+	pub fn recover_batch_host(
+		&self,
+		shards: &mut [u8],
+		shard_len: usize,
+		present: &[u8],
+		out: Option<&mut [u8]>,
+		restore: bool,
+		bad_rows: Option<&mut [u32]>,
+		mismatch: Option<&mut [u8]>,
+		status: Option<&mut [sys::np_payload_status]>,
+	) -> Result<()> {
+		let n = self.params.raw.n;
+		assert_eq!(present.len() % n, 0, "present must hold n flags per payload");
+		let batch = present.len() / n;
+		assert_eq!(shards.len(), batch * n * shard_len, "shards must hold n rows per payload");
+		let out_stride = shard_len / 2 * 2 * self.params.raw.k;
+		if let Some(o) = &out {
+			assert_eq!(o.len(), batch * out_stride, "out must hold every payload");
+		}
+		if let Some(b) = &bad_rows {
+			assert_eq!(b.len(), batch, "bad_rows must hold one count per payload");
+		}
+		if let Some(m) = &mismatch {
+			assert_eq!(m.len(), batch * n, "mismatch must hold n flags per payload");
+		}
+		if let Some(s) = &status {
+			assert_eq!(s.len(), batch, "status must hold one entry per payload");
+		}
+		check(unsafe {
+			sys::np_recover_batch_host(
+				self.ctx.raw,
+				&self.params.raw,
+				shards.as_mut_ptr(),
+				shard_len,
+				n * shard_len,
+				present.as_ptr(),
+				batch,
+				out.map_or(std::ptr::null_mut(), |o| o.as_mut_ptr()),
+				out_stride,
+				restore as std::os::raw::c_int,
+				bad_rows.map_or(std::ptr::null_mut(), |b| b.as_mut_ptr()),
+				mismatch.map_or(std::ptr::null_mut(), |m| m.as_mut_ptr()),
+				status.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr()),
+			)
+		})
+	}
+
 	/// The items of a ragged batch of payloads of `lens` bytes, packed one
 	/// after the other: payloads back to back, each item's `wanted_n` (encode)
 	/// or `n` (`rows`) shard rows after the previous item's.  Returns the items

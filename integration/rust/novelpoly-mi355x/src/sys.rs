@@ -372,6 +372,21 @@ extern "C" {
 		out: *mut u8,
 		out_stride: usize,
 	) -> c_int;
+	pub fn np_recover_batch_host(
+		ctx: *mut np_ctx,
+		params: *const np_code_params,
+		shards: *mut u8,
+		shard_len: usize,
+		batch_stride: usize,
+		present: *const u8,
+		batch: usize,
+		out: *mut u8,
+		out_stride: usize,
+		restore: c_int,
+		bad_rows: *mut u32,
+		mismatch: *mut u8,
+		status: *mut np_payload_status,
+	) -> c_int;
 
 	pub fn np_batch_split(batch: usize, ndev: usize, i: usize, begin: *mut usize, count: *mut usize);
 	pub fn np_encode_batch_multi(
@@ -420,6 +435,38 @@ extern "C" {
 		batch: usize,
 		out: *mut u8,
 		out_stride: usize,
+	) -> c_int;
+	pub fn np_recover_batch_multi(
+		ctxs: *const *mut np_ctx,
+		nctx: usize,
+		params: *const np_code_params,
+		d_shards: *const *mut u8,
+		shard_len: usize,
+		batch_stride: usize,
+		d_present: *const *const u8,
+		batch: usize,
+		d_out: *const *mut u8,
+		out_stride: usize,
+		restore: c_int,
+		d_bad_rows: *const *mut u32,
+		d_mismatch: *const *mut u8,
+		d_status: *const *mut np_payload_status,
+	) -> c_int;
+	pub fn np_recover_batch_host_multi(
+		ctxs: *const *mut np_ctx,
+		nctx: usize,
+		params: *const np_code_params,
+		shards: *mut u8,
+		shard_len: usize,
+		batch_stride: usize,
+		present: *const u8,
+		batch: usize,
+		out: *mut u8,
+		out_stride: usize,
+		restore: c_int,
+		bad_rows: *mut u32,
+		mismatch: *mut u8,
+		status: *mut np_payload_status,
 	) -> c_int;
 
 	pub fn np_afft_dev(ctx: *mut np_ctx, d_data: *mut u16, size: usize, index: usize, cols: usize, stream: *mut c_void) -> c_int;

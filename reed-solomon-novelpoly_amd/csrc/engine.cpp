@@ -658,7 +658,7 @@ int np_debug_bounds_check(np_ctx* c, uint32_t out[8]) {
   return NP_OK;
 }
 
-const char* np_version(void) { return "novelpoly-mi355x 0.6.0 (gfx950)"; }
+const char* np_version(void) { return "novelpoly-mi355x 0.7.0 (gfx950)"; }
 
 size_t np_recoverability_subset_size(size_t n) { return (n ? (n - 1) / 3 : 0) + 1; }
 
@@ -1145,6 +1145,25 @@ void copy_blocks(uint8_t* dst, size_t dstride, const uint8_t* src, size_t sstrid
   });
 }
 
+// np_recover_batch_dev after validation (defined with the device entry points
+// below); np_recover_batch_host runs it per sub-batch on the slot's buffers.
+hipError_t launch_recover(np_ctx* c, const np_code_params* p, uint8_t* d_shards, size_t shard_len, size_t bstride,
+                          const uint8_t* d_present, size_t batch, uint8_t* d_out, size_t out_stride, bool restore,
+                          uint32_t* d_bad_rows, uint8_t* d_mismatch, uint32_t* d_status, hipStream_t s);
+
+// Present rows of every payload of a host mask; the first payload with fewer
+// than k (mod.rs:171-180) fails the call when `need_all`, else is only marked
+// in `ok` (may be null).
+int count_present(const np_code_params* p, const uint8_t* present, size_t batch, bool need_all, uint8_t* ok) {
+  for (size_t b = 0; b < batch; ++b) {
+    size_t have = 0;
+    for (size_t v = 0; v < p->n; ++v) have += present[b * p->n + v] ? 1 : 0;
+    if (have < p->k && need_all) return fail(NP_ERR_NEED_MORE_SHARDS, have, p->k, p->n);
+    if (ok) ok[b] = have >= p->k;
+  }
+  return NP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1371,6 +1390,216 @@ int np_reconstruct_batch_host(np_ctx* c, const np_code_params* p, const uint8_t*
   for (int i = 0; i < npipe; ++i) ring.drain((slot + i) % npipe, e, copy_out);
   e = pipe_sync(c, e);
   stats.report(mode == Rows::Pack ? "reconstruct (pack)" : mode == Rows::Gather ? "reconstruct (gather)" : "reconstruct (2-D DMA)", sb, batch);
+  return dev_err(e);
+}
+
+// np_recover_batch_dev on a host-memory batch through the same pipeline.  Per
+// sub-batch, on its slot's stream:
+//  - in: host threads pack the present rows the device reads into the slot's
+//    pinned staging behind two offset lists -- where each packed row goes in the
+//    slot's n-row device layout, and which rows of that layout come back (the
+//    absent rows below wanted_n of decodable payloads); one DMA moves all of it
+//    and k_expand_rows puts the rows in place, as the reconstruct's pack mode;
+//  - compute: launch_recover on the slot layout, the payloads always into the
+//    slot's output buffer (no payload scratch of the context, also when the
+//    caller asks for no payloads), counts, map and statuses next to them;
+//  - out: k_pack_rows packs the rows of the second list behind the payloads, one
+//    DMA brings the requested part of that block into pinned staging, and when
+//    the slot's event has fired host threads scatter the rows into `shards` and
+//    copy the rest out.
+// Everything is staged: the caller's memory is never registered here and no
+// caller pointer reaches a HIP call, pinned or not.
+int np_recover_batch_host(np_ctx* c, const np_code_params* p, uint8_t* shards, size_t shard_len, size_t bstride,
+                          const uint8_t* present, size_t batch, uint8_t* out, size_t out_stride, int restore,
+                          uint32_t* bad_rows, uint8_t* mismatch, np_payload_status* status) {
+  if (!c) return fail(NP_ERR_INVALID_ARGUMENT);
+  int st = check_params(p);
+  if (st) return st;
+  if (shard_len == 0 || (shard_len & 1)) return fail(NP_ERR_EMPTY_SHARD);
+  if (!shards || !present || bstride < p->n * shard_len) return fail(NP_ERR_INVALID_ARGUMENT);
+  const size_t olen = (shard_len / 2) * 2 * p->k;
+  if ((!out && !restore && !bad_rows) || (mismatch && !bad_rows) || (out && out_stride < olen))
+    return fail(NP_ERR_INVALID_ARGUMENT);
+  if (batch == 0) return NP_OK;
+  // a payload with fewer than k present rows: reported through `status` and
+  // skipped by every host copy, or -- without `status` -- the call's error
+  std::vector<uint8_t> ok(batch);
+  st = count_present(p, present, batch, status == nullptr, ok.data());
+  if (st) return st;
+  const size_t n = p->n, wn = p->wanted_n, dstride = n * shard_len;
+  const bool verify = bad_rows != nullptr;
+  // rows shipped: the compare reads every present parity row; without it, what
+  // the reconstruct ships
+  const size_t rows = verify ? n : rows_needed(p, shard_len, present, batch);
+  const size_t span = std::max(rows, restore ? wn : 0), nblk = (span + 63) / 64;  // packing tasks per payload
+  // rows in and rows back, counted up to each payload
+  std::vector<size_t> in_at(batch + 1, 0), back_at(batch + 1, 0);
+  for (size_t b = 0; b < batch; ++b) {
+    size_t in = 0, back = 0;
+    if (ok[b]) {
+      const uint8_t* pr = present + b * n;
+      for (size_t v = 0; v < rows; ++v) in += pr[v] ? 1 : 0;
+      for (size_t v = 0; restore && v < wn; ++v) back += pr[v] ? 0 : 1;
+    }
+    in_at[b + 1] = in_at[b] + in;
+    back_at[b + 1] = back_at[b] + back;
+  }
+  // Sub-batches of about kPipeMovedBytes of PCIe traffic in both directions: the
+  // present rows in, the payloads and the restored rows out; NP_PIPE_SB
+  // (payloads) overrides.  Never counted below one payload's length, which the
+  // slot holds per payload whatever is requested: a batch that moves next to
+  // nothing (say, no payload decodes) still runs in bounded slots.
+  const size_t per = std::max(olen, (in_at[batch] + back_at[batch]) * shard_len / batch + (out ? olen : 0));
+  size_t sb = std::min(batch, std::max<size_t>(1, (kPipeMovedBytes + per - 1) / per));
+  if (const char* v = std::getenv("NP_PIPE_SB")) sb = std::min(batch, std::max<size_t>(1, std::strtoul(v, nullptr, 10)));
+  size_t max_in = 0, max_back = 0;
+  for (size_t b0 = 0; b0 < batch; b0 += sb) {
+    const size_t b1 = std::min(batch, b0 + sb);
+    max_in = std::max(max_in, in_at[b1] - in_at[b0]);
+    max_back = std::max(max_back, back_at[b1] - back_at[b0]);
+  }
+  const auto al = [](size_t x) { return (x + 255) / 256 * 256; };
+  // The slot's output block for `cnt` payloads with `tb` rows coming back:
+  // payloads, packed restored rows, counts, map, statuses; the requested part of
+  // it is one contiguous range.
+  struct OutBlock {
+    size_t rows, counts, map, status, end;
+  };
+  const auto out_block = [&](size_t cnt, size_t tb) {
+    OutBlock o{};
+    o.rows = al(cnt * olen);
+    o.counts = o.rows + al(tb * shard_len);
+    o.map = o.counts + al(verify ? cnt * sizeof(uint32_t) : 0);
+    o.status = o.map + al(mismatch ? cnt * n : 0);
+    o.end = o.status + cnt * kStatusBytes;
+    return o;
+  };
+  const size_t cap_in = al(max_in * 8) + al(max_back * 8) + max_in * shard_len;
+  const size_t cap_out = out_block(sb, max_back).end;
+  std::lock_guard<std::mutex> g(c->mu);
+  (void)hipSetDevice(c->device);
+  const int npipe = pipe_slots();
+  hipError_t e = pipe_init(c, npipe);
+  for (int i = 0; e == hipSuccess && i < npipe; ++i) {
+    e = HIP(c->pipe_in[i].ensure(sb * dstride));
+    if (e == hipSuccess) e = HIP(c->pipe_out[i].ensure(cap_out));
+    if (e == hipSuccess) e = HIP(c->pipe_cin[i].ensure(cap_in));
+    if (e == hipSuccess) e = HIP(c->pipe_hin[i].ensure(cap_in));
+    if (e == hipSuccess) e = HIP(c->pipe_hout[i].ensure(cap_out));
+  }
+  // the whole present mask up front, through pinned staging, before any
+  // sub-batch reads it
+  if (e == hipSuccess) e = HIP(c->pipe_pres.ensure(batch * n));
+  if (e == hipSuccess) e = HIP(c->h_pres.ensure(batch * n));
+  if (e == hipSuccess) {
+    std::memcpy(c->h_pres.p, present, batch * n);
+    e = HIP(hipMemcpyAsync(c->pipe_pres.p, c->h_pres.p, batch * n, hipMemcpyHostToDevice, c->pipe_s[0]));
+  }
+  if (e == hipSuccess) e = HIP(hipStreamSynchronize(c->pipe_s[0]));
+  PipeStats stats;
+  SlotRing ring{c, &stats};
+  // where the packed rows of the sub-batch in flight on each slot go in `shards`
+  std::vector<size_t> back_host[np_ctx::kPipe];
+  constexpr size_t kScatter = 16;  // rows per scatter task
+  auto copy_out = [&](size_t b0, size_t cnt, int sl) {  // staged outputs -> the caller's buffers
+    const std::vector<size_t>& dst = back_host[sl];
+    const OutBlock o = out_block(cnt, dst.size());
+    const uint8_t* h = c->pipe_hout[sl].as<uint8_t>();
+    if (out) {
+      const size_t pieces = (olen + (size_t(1) << 20) - 1) >> 20;
+      parallel_for(cnt * pieces, [&](size_t i) {
+        const size_t b = i / pieces, off = (i % pieces) << 20, l = std::min<size_t>(olen - off, size_t(1) << 20);
+        if (ok[b0 + b]) stream_copy(out + (b0 + b) * out_stride + off, h + b * olen + off, l);
+      });
+    }
+    parallel_for((dst.size() + kScatter - 1) / kScatter, [&](size_t t) {
+      for (size_t j = t * kScatter; j < std::min(dst.size(), (t + 1) * kScatter); ++j)
+        stream_copy(shards + dst[j], h + o.rows + j * shard_len, shard_len);
+    });
+    if (verify) std::memcpy(bad_rows + b0, h + o.counts, cnt * sizeof(uint32_t));
+    if (mismatch) std::memcpy(mismatch + b0 * n, h + o.map, cnt * n);
+    if (status) std::memcpy(status + b0, h + o.status, cnt * kStatusBytes);
+  };
+  std::vector<size_t> base_in, base_back;  // packed index of the first row of each (payload, 64-row block)
+  int slot = 0;
+  for (size_t b0 = 0; e == hipSuccess && b0 < batch; b0 += sb, slot = (slot + 1) % npipe) {
+    const size_t cnt = std::min(sb, batch - b0);
+    hipStream_t s = c->pipe_s[slot];
+    uint8_t* din = c->pipe_in[slot].as<uint8_t>();
+    uint8_t* dout = c->pipe_out[slot].as<uint8_t>();
+    const uint8_t* dpres = c->pipe_pres.as<uint8_t>() + b0 * n;
+    ring.drain(slot, e, copy_out);  // the slot's staging is free again
+    if (e != hipSuccess) break;
+    const size_t tin = in_at[b0 + cnt] - in_at[b0], tb = back_at[b0 + cnt] - back_at[b0];
+    const size_t list_in = al(tin * 8), list_back = al(tb * 8);
+    const OutBlock o = out_block(cnt, tb);
+    back_host[slot].resize(tb);
+    uint8_t* cin = c->pipe_cin[slot].as<uint8_t>();
+    if (tin) {
+      base_in.assign(cnt * nblk + 1, 0);
+      base_back.assign(cnt * nblk + 1, 0);
+      for (size_t t = 0; t < cnt * nblk; ++t) {
+        const size_t b = b0 + t / nblk, v0 = 64 * (t % nblk), v1 = std::min(span, v0 + 64);
+        const uint8_t* pr = present + b * n;
+        size_t in = 0, back = 0;
+        for (size_t v = v0; ok[b] && v < v1; ++v) {
+          in += v < rows && pr[v] ? 1 : 0;
+          back += restore && v < wn && !pr[v] ? 1 : 0;
+        }
+        base_in[t + 1] = base_in[t] + in;
+        base_back[t + 1] = base_back[t] + back;
+      }
+      uint8_t* h = c->pipe_hin[slot].as<uint8_t>();
+      uint64_t* in_list = reinterpret_cast<uint64_t*>(h);
+      uint64_t* back_list = reinterpret_cast<uint64_t*>(h + list_in);
+      uint8_t* data = h + list_in + list_back;
+      size_t* back_dst = back_host[slot].data();
+      const uint8_t* src = shards + b0 * bstride;
+      const auto tp = std::chrono::steady_clock::now();
+      parallel_for(cnt * nblk, [&](size_t t) {
+        const size_t b = t / nblk, v0 = 64 * (t % nblk), v1 = std::min(span, v0 + 64);
+        if (!ok[b0 + b]) return;
+        const uint8_t* pr = present + (b0 + b) * n;
+        size_t j = base_in[t], q = base_back[t];
+        for (size_t v = v0; v < v1; ++v) {
+          if (pr[v]) {
+            if (v >= rows) continue;
+            stream_copy(data + j * shard_len, src + b * bstride + v * shard_len, shard_len);
+            in_list[j++] = b * dstride + v * shard_len;
+          } else if (restore && v < wn) {
+            back_dst[q] = (b0 + b) * bstride + v * shard_len;
+            back_list[q++] = b * dstride + v * shard_len;
+          }
+        }
+      });
+      stats.pack += PipeStats::ms(tp);
+      e = HIP(hipMemcpyAsync(cin, h, list_in + list_back + tin * shard_len, hipMemcpyHostToDevice, s));
+      e = after(e, s, __LINE__, "packed rows H2D");
+      if (e == hipSuccess)
+        e = HIP(np::launch_expand_rows(cin + list_in + list_back, reinterpret_cast<const uint64_t*>(cin), din, shard_len,
+                                       tin, s));
+      e = after(e, s, __LINE__, "packed rows expand");
+    }
+    if (e == hipSuccess)
+      e = HIP(launch_recover(c, p, din, shard_len, dstride, dpres, cnt, dout, olen, restore != 0,
+                             verify ? reinterpret_cast<uint32_t*>(dout + o.counts) : nullptr,
+                             mismatch ? dout + o.map : nullptr, reinterpret_cast<uint32_t*>(dout + o.status), s));
+    e = after(e, s, __LINE__, "recover kernels");
+    if (e == hipSuccess && tb)
+      e = HIP(np::launch_pack_rows(din, reinterpret_cast<const uint64_t*>(cin + list_in), dout + o.rows, shard_len, tb, s));
+    e = after(e, s, __LINE__, "restored rows pack");
+    // the requested part of the block: from the payloads or the rows behind
+    // them, up to the statuses or their start
+    const size_t lo = out ? 0 : o.rows, hi = status ? o.end : o.status;
+    if (e == hipSuccess && hi > lo)
+      e = HIP(hipMemcpyAsync(c->pipe_hout[slot].as<uint8_t>() + lo, dout + lo, hi - lo, hipMemcpyDeviceToHost, s));
+    e = after(e, s, __LINE__, "outputs D2H");
+    if (e == hipSuccess) e = ring.mark(slot, s, b0, cnt);
+  }
+  // the pending slots, oldest first (a failed call still waits for its streams)
+  for (int i = 0; i < npipe; ++i) ring.drain((slot + i) % npipe, e, copy_out);
+  e = pipe_sync(c, e);
+  stats.report("recover (pack)", sb, batch);
   return dev_err(e);
 }
 
@@ -2848,6 +3077,47 @@ int np_reconstruct_batch_host_multi(np_ctx* const* ctxs, size_t nctx, const np_c
   return run_multi(ctxs, nctx, batch, [&](size_t i, size_t b0, size_t cnt) {
     return np_reconstruct_batch_host(ctxs[i], p, shards + b0 * bstride, shard_len, bstride, present + b0 * p->n,
                                      cnt, out + b0 * out_stride, out_stride);
+  });
+}
+
+int np_recover_batch_multi(np_ctx* const* ctxs, size_t nctx, const np_code_params* p, uint8_t* const* d_shards,
+                           size_t shard_len, size_t bstride, const uint8_t* const* d_present, size_t batch,
+                           uint8_t* const* d_out, size_t out_stride, int restore, uint32_t* const* d_bad_rows,
+                           uint8_t* const* d_mismatch, np_payload_status* const* d_status) {
+  if (!d_shards || !d_present) return fail(NP_ERR_INVALID_ARGUMENT);
+  if (int st = check_params(p)) return st;
+  return run_multi(ctxs, nctx, batch, [&](size_t i, size_t, size_t cnt) {
+    int st = np_recover_batch_dev(ctxs[i], p, d_shards[i], shard_len, bstride, d_present[i], cnt,
+                                  d_out ? d_out[i] : nullptr, out_stride, restore, d_bad_rows ? d_bad_rows[i] : nullptr,
+                                  d_mismatch ? d_mismatch[i] : nullptr, d_status ? d_status[i] : nullptr,
+                                  ctxs[i]->stream);
+    return st ? st : np_ctx_synchronize(ctxs[i]);
+  });
+}
+
+int np_recover_batch_host_multi(np_ctx* const* ctxs, size_t nctx, const np_code_params* p, uint8_t* shards,
+                                size_t shard_len, size_t bstride, const uint8_t* present, size_t batch, uint8_t* out,
+                                size_t out_stride, int restore, uint32_t* bad_rows, uint8_t* mismatch,
+                                np_payload_status* status) {
+  if (!shards || !present) return fail(NP_ERR_INVALID_ARGUMENT);
+  if (int st = check_params(p)) return st;
+  // without `status` a payload short of k rows fails the whole call, as the
+  // single-device call: checked once over the batch, before any worker starts
+  // (behind the checks that precede it there)
+  if (!status && ctxs && nctx) {
+    if (shard_len == 0 || (shard_len & 1)) return fail(NP_ERR_EMPTY_SHARD);
+    if (bstride < p->n * shard_len || (!out && !restore && !bad_rows) || (mismatch && !bad_rows) ||
+        (out && out_stride < (shard_len / 2) * 2 * p->k))
+      return fail(NP_ERR_INVALID_ARGUMENT);
+    if (int st = count_present(p, present, batch, true, nullptr)) return st;
+  }
+  // no caller memory is registered, so the ranges share nothing: each worker
+  // takes its part of the one buffer set
+  return run_multi(ctxs, nctx, batch, [&](size_t i, size_t b0, size_t cnt) {
+    return np_recover_batch_host(ctxs[i], p, shards + b0 * bstride, shard_len, bstride, present + b0 * p->n, cnt,
+                                 out ? out + b0 * out_stride : nullptr, out_stride, restore,
+                                 bad_rows ? bad_rows + b0 : nullptr, mismatch ? mismatch + b0 * p->n : nullptr,
+                                 status ? status + b0 : nullptr);
   });
 }
 

@@ -87,6 +87,11 @@ hipError_t launch_copy_rows(const uint8_t* src, size_t sstride, uint8_t* dst, si
 // put in their n-row device layout.  row_bytes even.
 hipError_t launch_expand_rows(const uint8_t* src, const uint64_t* dst_off, uint8_t* dst, size_t row_bytes,
                               size_t nrows, hipStream_t s);
+// The inverse: row j of dst (row_bytes each, rows packed one after the other)
+// = src + src_off[j], for j < nrows: the restored rows of a staged host recover
+// gathered from their n-row device layout.  row_bytes even.
+hipError_t launch_pack_rows(const uint8_t* src, const uint64_t* src_off, uint8_t* dst, size_t row_bytes, size_t nrows,
+                            hipStream_t s);
 
 // ---- fast path (kernels_fast.hip) ----
 // Returns true if a specialised kernel serves (n, k).

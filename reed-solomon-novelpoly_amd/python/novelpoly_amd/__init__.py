@@ -99,12 +99,18 @@ def lib() -> C.CDLL:
             "np_reconstruct_from_systematic_batch_dev": (C.c_int, [vp, P, vp, _sz, _sz, _sz, vp, _sz, vp]),
             "np_encode_batch_host": (C.c_int, [vp, P, vp, _sz, _sz, _sz, vp, _sz]),
             "np_reconstruct_batch_host": (C.c_int, [vp, P, vp, _sz, _sz, vp, _sz, vp, _sz]),
+            "np_recover_batch_host": (C.c_int, [vp, P, vp, _sz, _sz, vp, _sz, vp, _sz, C.c_int, vp, vp, vp]),
             "np_batch_split": (None, [_sz, _sz, _sz, C.POINTER(_sz), C.POINTER(_sz)]),
             "np_encode_batch_multi": (C.c_int, [C.POINTER(vp), _sz, P, C.POINTER(vp), _sz, _sz, _sz, C.POINTER(vp), _sz]),
             "np_reconstruct_batch_multi": (C.c_int, [C.POINTER(vp), _sz, P, C.POINTER(vp), _sz, _sz, C.POINTER(vp), _sz,
                                                      C.POINTER(vp), _sz, C.POINTER(vp)]),
             "np_encode_batch_host_multi": (C.c_int, [C.POINTER(vp), _sz, P, vp, _sz, _sz, _sz, vp, _sz]),
             "np_reconstruct_batch_host_multi": (C.c_int, [C.POINTER(vp), _sz, P, vp, _sz, _sz, vp, _sz, vp, _sz]),
+            "np_recover_batch_multi": (C.c_int, [C.POINTER(vp), _sz, P, C.POINTER(vp), _sz, _sz, C.POINTER(vp), _sz,
+                                                 C.POINTER(vp), _sz, C.c_int, C.POINTER(vp), C.POINTER(vp),
+                                                 C.POINTER(vp)]),
+            "np_recover_batch_host_multi": (C.c_int, [C.POINTER(vp), _sz, P, vp, _sz, _sz, vp, _sz, vp, _sz, C.c_int, vp,
+                                                      vp, vp]),
             "np_afft_dev": (C.c_int, [vp, vp, _sz, _sz, _sz, vp]),
             "np_inverse_afft_dev": (C.c_int, [vp, vp, _sz, _sz, _sz, vp]),
             "np_walsh_dev": (C.c_int, [vp, vp, _sz, vp]),
@@ -737,6 +743,23 @@ def reconstruct_batch_host(params: CodeParams, shards: int, shard_len: int, batc
                                            batch, out, out_stride))
 
 
+def recover_batch_host(params: CodeParams, shards: int, shard_len: int, batch_stride: int, present: int, batch: int,
+                       ctx: Optional[Context] = None, out: int = 0, out_stride: int = 0, restore: bool = False,
+                       bad_rows: int = 0, mismatch: int = 0, status: int = 0) -> None:
+    """:func:`recover_batch_dev` on host buffers (np_recover_batch_host; addresses
+    of host memory, 0 = not given), pipelined like :func:`reconstruct_batch_host`:
+    the payloads into ``out``, the absent rows below ``wanted_n`` into ``shards``
+    (``restore``) and the verdict into ``bad_rows`` / ``mismatch``, each bit for
+    bit the device call's.  With ``status`` (``batch`` np_payload_status entries)
+    a payload with fewer than k present rows is reported there and left
+    untouched; without it such a payload raises :class:`NeedMoreShards` before
+    anything is written.  Returns when every output is in host memory."""
+    ctx = ctx or default_context()
+    _raise(lib().np_recover_batch_host(ctx.handle, C.byref(params._c()), shards or None, shard_len, batch_stride,
+                                       present or None, batch, out or None, out_stride, 1 if restore else 0,
+                                       bad_rows or None, mismatch or None, status or None))
+
+
 def reconstruct_from_systematic_batch_dev(params: CodeParams, d_shards: int, shard_len: int, batch_stride: int,
                                           batch: int, d_out: int, out_stride: int, ctx: Optional[Context] = None,
                                           stream: int = 0) -> None:
@@ -801,6 +824,28 @@ def reconstruct_batch_host_multi(ctxs, params: CodeParams, shards: int, shard_le
                                  present: int, batch: int, out: int, out_stride: int) -> None:
     _raise(lib().np_reconstruct_batch_host_multi(_ctx_array(ctxs), len(ctxs), C.byref(params._c()), shards, shard_len,
                                                  batch_stride, present, batch, out, out_stride))
+
+
+def recover_batch_multi(ctxs, params: CodeParams, d_shards, shard_len: int, batch_stride: int, d_present, batch: int,
+                        d_out=None, out_stride: int = 0, restore: bool = False, d_bad_rows=None, d_mismatch=None,
+                        d_status=None) -> None:
+    """:func:`recover_batch_dev` over several contexts (np_recover_batch_multi):
+    every buffer argument is a list with device i's address for its range
+    (:func:`batch_split`); None = that output is not requested."""
+    opt = [_ptr_array(a) if a else None for a in (d_out, d_bad_rows, d_mismatch, d_status)]
+    _raise(lib().np_recover_batch_multi(_ctx_array(ctxs), len(ctxs), C.byref(params._c()), _ptr_array(d_shards),
+                                        shard_len, batch_stride, _ptr_array(d_present), batch, opt[0], out_stride,
+                                        1 if restore else 0, opt[1], opt[2], opt[3]))
+
+
+def recover_batch_host_multi(ctxs, params: CodeParams, shards: int, shard_len: int, batch_stride: int, present: int,
+                             batch: int, out: int = 0, out_stride: int = 0, restore: bool = False, bad_rows: int = 0,
+                             mismatch: int = 0, status: int = 0) -> None:
+    """:func:`recover_batch_host` with the batch split over several contexts
+    (np_recover_batch_host_multi): one buffer set, each context its range."""
+    _raise(lib().np_recover_batch_host_multi(_ctx_array(ctxs), len(ctxs), C.byref(params._c()), shards or None,
+                                             shard_len, batch_stride, present or None, batch, out or None, out_stride,
+                                             1 if restore else 0, bad_rows or None, mismatch or None, status or None))
 
 
 # ---------------------------------------------------- low-level hooks ----
