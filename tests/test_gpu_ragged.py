@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 import novelpoly_amd as npa
+from _stream_gate import Gate, run_gated
 
 pytestmark = pytest.mark.gpu
 
@@ -295,26 +296,36 @@ def test_equal_lengths_match_the_uniform_calls(gpu, nw, kw):
 def test_back_to_back_calls_keep_their_plans(gpu, oracle, nw, kw):
     """Two encodes and two reconstructs queued on one stream with different
     items and no synchronisation in between: each call's plan must outlive the
-    next call's upload."""
+    next call's upload.  A gate in front (tests/_stream_gate.py) keeps the first
+    call from starting before the last one is enqueued."""
+    import torch
+
     c1 = _case(oracle, nw, kw, 11)
     c2 = _case(oracle, nw, kw, 8)
     r1 = _recv_case(oracle, nw, kw, 11)
     r2 = _recv_case(oracle, nw, kw, 8)
     s = _stream()
-    pay1, pay2 = _dev(c1.payloads), _dev(c2.payloads)
-    e1, e2 = _dev(np.full(c1.ssize, FILL, np.uint8)), _dev(np.full(c2.ssize, FILL, np.uint8))
-    b1, b2, p1, p2 = _dev(r1[0]), _dev(r2[0]), _dev(r1[1]), _dev(r2[1])
-    o1, o2 = _dev(np.full(c1.psize, FILL, np.uint8)), _dev(np.full(c2.psize, FILL, np.uint8))
-    npa.encode_ragged_dev(c1.p, pay1.data_ptr(), c1.psize, e1.data_ptr(), c1.ssize, c1.items, ctx=gpu, stream=s)
-    npa.encode_ragged_dev(c2.p, pay2.data_ptr(), c2.psize, e2.data_ptr(), c2.ssize, c2.items, ctx=gpu, stream=s)
-    npa.reconstruct_ragged_dev(c1.p, b1.data_ptr(), c1.ssize, p1.data_ptr(), o1.data_ptr(), c1.psize, c1.items,
-                               ctx=gpu, stream=s)
-    npa.reconstruct_ragged_dev(c2.p, b2.data_ptr(), c2.ssize, p2.data_ptr(), o2.data_ptr(), c2.psize, c2.items,
-                               ctx=gpu, stream=s)
-    _diff(_host(e1), c1.shards, "first encode")
-    _diff(_host(e2), c2.shards, "second encode")
-    _diff(_host(o1), r1[2], "first reconstruct")
-    _diff(_host(o2), r2[2], "second reconstruct")
+
+    def case(gate_ms):
+        pay1, pay2 = _dev(c1.payloads), _dev(c2.payloads)
+        e1, e2 = _dev(np.full(c1.ssize, FILL, np.uint8)), _dev(np.full(c2.ssize, FILL, np.uint8))
+        b1, b2, p1, p2 = _dev(r1[0]), _dev(r2[0]), _dev(r1[1]), _dev(r2[1])
+        o1, o2 = _dev(np.full(c1.psize, FILL, np.uint8)), _dev(np.full(c2.psize, FILL, np.uint8))
+        g = Gate(torch.cuda.current_stream(), gate_ms)
+        npa.encode_ragged_dev(c1.p, pay1.data_ptr(), c1.psize, e1.data_ptr(), c1.ssize, c1.items, ctx=gpu, stream=s)
+        npa.encode_ragged_dev(c2.p, pay2.data_ptr(), c2.psize, e2.data_ptr(), c2.ssize, c2.items, ctx=gpu, stream=s)
+        npa.reconstruct_ragged_dev(c1.p, b1.data_ptr(), c1.ssize, p1.data_ptr(), o1.data_ptr(), c1.psize, c1.items,
+                                   ctx=gpu, stream=s)
+        npa.reconstruct_ragged_dev(c2.p, b2.data_ptr(), c2.ssize, p2.data_ptr(), o2.data_ptr(), c2.psize, c2.items,
+                                   ctx=gpu, stream=s)
+        ms, held = g.host_ms(), g.open()
+        _diff(_host(e1), c1.shards, "first encode")
+        _diff(_host(e2), c2.shards, "second encode")
+        _diff(_host(o1), r1[2], "first reconstruct")
+        _diff(_host(o2), r2[2], "second reconstruct")
+        return held, ms
+
+    run_gated(case, label=f"ragged back to back {nw},{kw}")
 
 
 def test_batch_zero_and_validation_on_the_device_calls(gpu):

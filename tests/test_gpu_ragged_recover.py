@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 
 import novelpoly_amd as npa
+from _stream_gate import Gate, run_gated
 from test_gpu_ragged import BATCHES, FILL, _diff, _host, _stream
 from test_gpu_ragged_masked import (ROTS, SHAPES, _dev, _items, _mcase, _restore_pattern, _stage, _verify_pattern)
 from test_gpu_verify import GUARD, UNDECODABLE, _flip
@@ -294,7 +295,8 @@ def test_equals_the_three_ragged_calls(gpu, oracle, nw, kw):
 def test_back_to_back_calls_keep_their_plans(gpu, oracle, nw, kw):
     """Four calls with different requests and items queued on one stream with no
     synchronisation in between: each call's plan, records and scratch must
-    outlive the next call's."""
+    outlive the next call's.  A gate in front (tests/_stream_gate.py) keeps the
+    first call from starting before the last one is enqueued."""
     import torch
 
     c1, c2 = _mcase(oracle, nw, kw, 11), _mcase(oracle, nw, kw, 8)
@@ -302,22 +304,29 @@ def test_back_to_back_calls_keep_their_plans(gpu, oracle, nw, kw):
     s = _stream()
     requests = [(c1, e1, True, True, True), (c2, e2, False, True, True), (c1, e1, True, False, True),
                 (c2, e2, True, True, False)]
-    held = []
-    for c, e, with_out, restore, verify in requests:
-        batch = len(c.items)
-        held.append((_dev(e.before), _dev(e.pres), torch.full((c.psize,), GUARD, dtype=torch.uint8, device="cuda"),
-                     torch.full((4 * batch,), GUARD, dtype=torch.uint8, device="cuda"),
-                     torch.full((batch, c.n), GUARD, dtype=torch.uint8, device="cuda"),
-                     torch.full((batch, 2), -1, dtype=torch.int32, device="cuda")))
-    torch.cuda.synchronize()
-    for (c, e, with_out, restore, verify), (buf, pr, out, cnt, mp, st) in zip(requests, held):
-        npa.recover_ragged_dev(c.p, buf.data_ptr(), c.ssize, pr.data_ptr(), _out_items(c) if with_out else _items(c),
-                               d_out=out.data_ptr() if with_out else 0, out_size=c.psize if with_out else 0,
-                               restore=restore, d_bad_rows=cnt.data_ptr() if verify else 0,
-                               d_mismatch=mp.data_ptr() if verify else 0, d_status=st.data_ptr(), ctx=gpu, stream=s)
-    for j, ((c, e, with_out, restore, verify), (buf, pr, out, cnt, mp, st)) in enumerate(zip(requests, held)):
-        res = (_host(buf), _host(out), _host(cnt), _host(mp), _host(st))
-        _check(c, e, res, with_out, restore, verify, True, verify, f"call {j}")
+
+    def case(gate_ms):
+        held = []
+        for c, e, with_out, restore, verify in requests:
+            batch = len(c.items)
+            held.append((_dev(e.before), _dev(e.pres), torch.full((c.psize,), GUARD, dtype=torch.uint8, device="cuda"),
+                         torch.full((4 * batch,), GUARD, dtype=torch.uint8, device="cuda"),
+                         torch.full((batch, c.n), GUARD, dtype=torch.uint8, device="cuda"),
+                         torch.full((batch, 2), -1, dtype=torch.int32, device="cuda")))
+        torch.cuda.synchronize()
+        g = Gate(torch.cuda.current_stream(), gate_ms)
+        for (c, e, with_out, restore, verify), (buf, pr, out, cnt, mp, st) in zip(requests, held):
+            npa.recover_ragged_dev(c.p, buf.data_ptr(), c.ssize, pr.data_ptr(), _out_items(c) if with_out else _items(c),
+                                   d_out=out.data_ptr() if with_out else 0, out_size=c.psize if with_out else 0,
+                                   restore=restore, d_bad_rows=cnt.data_ptr() if verify else 0,
+                                   d_mismatch=mp.data_ptr() if verify else 0, d_status=st.data_ptr(), ctx=gpu, stream=s)
+        ms, premise = g.host_ms(), g.open()
+        for j, ((c, e, with_out, restore, verify), (buf, pr, out, cnt, mp, st)) in enumerate(zip(requests, held)):
+            res = (_host(buf), _host(out), _host(cnt), _host(mp), _host(st))
+            _check(c, e, res, with_out, restore, verify, True, verify, f"call {j}")
+        return premise, ms
+
+    run_gated(case, label=f"ragged recover back to back {nw},{kw}")
 
 
 def test_batch_zero_and_null_pointers_on_the_device_call(gpu):
