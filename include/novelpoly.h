@@ -83,6 +83,19 @@ size_t np_shard_len(const np_code_params* params, size_t payload_size);
 /* mod.rs:64-71 CodeParams::is_faster8 analogue: 1 if specialised GPU kernels serve both
    directions of (n,k) for 1 MiB payloads (fast, small, resident, huge or big kernels) */
 int np_is_fast_path(const np_code_params* params);
+/* The kernel families of the engine's dispatch: the generic LOG/EXP-gather
+ * kernels, the small (k <= 32), fast (k = 64 .. 256), resident (k = 512 / 1024), big
+ * (k = 512 .. 2048) and sub-transform ("huge", k = 2048 .. 16384) kernels.  (An enum tag only:
+ * in C a typedef of this name would collide with the function below.) */
+enum np_kernel_family { NP_FAMILY_GENERIC = 0, NP_FAMILY_SMALL = 1, NP_FAMILY_FAST = 2,
+                        NP_FAMILY_RES = 3, NP_FAMILY_BIG = 4, NP_FAMILY_HUGE = 5 };
+/* The kernel family an encode (reconstruct == 0) or a reconstruct of rows of shard_len bytes runs on
+ * in this process (the NP_RES / NP_HUGE switches as read; NP_REC_RES256 per call); -1 for invalid params.
+ * No device needed.  It is the dispatch's own choice (engine.cpp enc_path / rec_path), so restore,
+ * verify, recover and the ragged calls, which run a reconstruct and an ordinary encode at k >= 512,
+ * follow it too.  (The sub-transform kernels' pairing of narrow payloads, NP_HUGE_PAIR, is a launch
+ * geometry inside one family and is not reported.) */
+int np_kernel_family(const np_code_params* params, size_t shard_len, int reconstruct);
 
 /* ---- context ------------------------------------------------------------- */
 typedef struct np_ctx np_ctx;

@@ -54,6 +54,14 @@ pub const NP_ERR_DEVICE: c_int = 101;
 pub const NP_ERR_ALLOC: c_int = 102;
 pub const NP_ERR_NO_DEVICE: c_int = 103;
 
+/// `enum np_kernel_family`: what `np_kernel_family` answers (-1: invalid parameters).
+pub const NP_FAMILY_GENERIC: c_int = 0;
+pub const NP_FAMILY_SMALL: c_int = 1;
+pub const NP_FAMILY_FAST: c_int = 2;
+pub const NP_FAMILY_RES: c_int = 3;
+pub const NP_FAMILY_BIG: c_int = 4;
+pub const NP_FAMILY_HUGE: c_int = 5;
+
 extern "C" {
 	pub fn np_last_error_detail(out: *mut usize);
 	pub fn np_last_error_site() -> *const c_char;
@@ -64,6 +72,7 @@ extern "C" {
 	pub fn np_params_new(n: usize, k: usize, wanted_n: usize, out: *mut np_code_params) -> c_int;
 	pub fn np_shard_len(params: *const np_code_params, payload_size: usize) -> usize;
 	pub fn np_is_fast_path(params: *const np_code_params) -> c_int;
+	pub fn np_kernel_family(params: *const np_code_params, shard_len: usize, reconstruct: c_int) -> c_int;
 
 	pub fn np_ctx_create(device: c_int, out: *mut *mut np_ctx) -> c_int;
 	pub fn np_ctx_destroy(ctx: *mut np_ctx);

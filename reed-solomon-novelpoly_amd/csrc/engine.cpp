@@ -334,12 +334,30 @@ RecPath rec_path(uint32_t n, uint32_t k, size_t shard_len) {
   return RecPath::Generic;
 }
 
+// A FastRes decode in the resident geometry (k = 512 / 1024; k = 256 with
+// NP_REC_RES256=1) instead of the fast / small kernels.
+bool rec_on_res(uint32_t n, uint32_t k) { return !np::fast_reconstruct_supported(n, k) || np::res256_reconstruct(n, k); }
+
+// The kernel family an encode of (n, k) into shards of shard_len bytes runs on,
+// chosen once for launch_encode, np_is_fast_path and np_kernel_family.
+enum class EncPath { Fast, Res, Huge, Big, Generic };
+
+EncPath enc_path(uint32_t n, uint32_t k, size_t shard_len) {
+  if (np::fast_encode_supported(n, k)) return EncPath::Fast;
+  if (np::res_encode_supported(n, k) && np::res_enabled()) return EncPath::Res;
+  if (np::huge_encode_supported(n, k) && huge_on(k) &&
+      np::huge_encode_scratch_per_payload(shard_len, n, k) <= kBigScratchMin)
+    return EncPath::Huge;
+  if (np::big_encode_supported(n, k)) return EncPath::Big;
+  return EncPath::Generic;
+}
+
 // Caller holds the context lock.
 hipError_t launch_encode(np_ctx* c, const np::EncodeArgs& a, hipStream_t s) {
-  if (np::fast_encode_supported(a.n, a.k)) return HIP(np::launch_encode_fast(c->T, a, s));
-  if (np::res_encode_supported(a.n, a.k) && np::res_enabled()) return HIP(np::launch_encode_res(c->T, a, s));
-  const size_t huge_per = np::huge_encode_scratch_per_payload(a.shard_len, a.n, a.k);
-  if (np::huge_encode_supported(a.n, a.k) && huge_on(a.k) && huge_per <= kBigScratchMin) {
+  const EncPath path = enc_path(a.n, a.k, a.shard_len);
+  if (path == EncPath::Fast) return HIP(np::launch_encode_fast(c->T, a, s));
+  if (path == EncPath::Res) return HIP(np::launch_encode_res(c->T, a, s));
+  if (path == EncPath::Huge) {
     // slices of the batch whose tile slots fit the context scratch
     const size_t per = huge_slice(c, np::huge_encode_scratch(2, a.payload_len, a.n, a.k), 0);
     for (size_t b0 = 0; b0 < a.batch; b0 += per) {
@@ -356,7 +374,7 @@ hipError_t launch_encode(np_ctx* c, const np::EncodeArgs& a, hipStream_t s) {
     }
     return hipSuccess;
   }
-  if (np::big_encode_supported(a.n, a.k)) {
+  if (path == EncPath::Big) {
     const size_t tiles = ((a.payload_len + 2 * a.k - 1) / (2 * a.k) + 255) / 256;
     uint8_t* scr = nullptr;
     size_t bytes = 0;
@@ -390,7 +408,7 @@ constexpr size_t kStatusBytes = 2 * sizeof(uint32_t);  // per payload (launchers
 hipError_t launch_reconstruct(np_ctx* c, const np::ReconstructArgs& a, hipStream_t s) {
   const size_t own_status = a.status ? 0 : kStatusBytes;  // scratch bytes per payload for the status
   const RecPath path = rec_path(a.n, a.k, a.shard_len);
-  const bool res = !np::fast_reconstruct_supported(a.n, a.k) || np::res256_reconstruct(a.n, a.k);
+  const bool res = rec_on_res(a.n, a.k);
   if (path == RecPath::FastRes) {
     // per-payload decode rows + row multipliers and their tables (from the
     // caller's locators when given) and the status, then the decode
@@ -697,11 +715,32 @@ size_t np_shard_len(const np_code_params* p, size_t payload_size) {
 int np_is_fast_path(const np_code_params* p) {
   if (!p) return 0;
   const uint32_t n = static_cast<uint32_t>(p->n), k = static_cast<uint32_t>(p->k);
-  const bool enc = np::fast_encode_supported(n, k) || (np::res_encode_supported(n, k) && np::res_enabled()) ||
-                   (np::huge_encode_supported(n, k) && huge_on(k)) || np::big_encode_supported(n, k);
-  // the reconstruct family for a 1 MiB payload (the huge kernels' tile slots
-  // depend on the shard length: far longer shards fall to the generic decode)
-  return (enc && rec_path(n, k, np_shard_len(p, size_t(1) << 20)) != RecPath::Generic) ? 1 : 0;
+  // the families for a 1 MiB payload (the huge kernels' tile slots depend on
+  // the shard length: far longer shards fall to the big / generic kernels)
+  const size_t sl = np_shard_len(p, size_t(1) << 20);
+  return (enc_path(n, k, sl) != EncPath::Generic && rec_path(n, k, sl) != RecPath::Generic) ? 1 : 0;
+}
+
+int np_kernel_family(const np_code_params* p, size_t shard_len, int reconstruct) {
+  if (check_params(p) != NP_OK) return -1;
+  const uint32_t n = static_cast<uint32_t>(p->n), k = static_cast<uint32_t>(p->k);
+  if (reconstruct) {
+    switch (rec_path(n, k, shard_len)) {
+      case RecPath::FastRes: return rec_on_res(n, k) ? NP_FAMILY_RES : k <= 32 ? NP_FAMILY_SMALL : NP_FAMILY_FAST;
+      case RecPath::Huge: return NP_FAMILY_HUGE;
+      case RecPath::Big: return NP_FAMILY_BIG;
+      case RecPath::Generic: return NP_FAMILY_GENERIC;
+    }
+    return -1;
+  }
+  switch (enc_path(n, k, shard_len)) {
+    case EncPath::Fast: return k <= 32 ? NP_FAMILY_SMALL : NP_FAMILY_FAST;
+    case EncPath::Res: return NP_FAMILY_RES;
+    case EncPath::Huge: return NP_FAMILY_HUGE;
+    case EncPath::Big: return NP_FAMILY_BIG;
+    case EncPath::Generic: return NP_FAMILY_GENERIC;
+  }
+  return -1;
 }
 
 int np_ctx_create(int device, np_ctx** out) {

@@ -64,6 +64,7 @@ def lib() -> C.CDLL:
             "np_params_new": (C.c_int, [_sz, _sz, _sz, P]),
             "np_shard_len": (_sz, [P, _sz]),
             "np_is_fast_path": (C.c_int, [P]),
+            "np_kernel_family": (C.c_int, [P, _sz, C.c_int]),
             "np_ctx_create": (C.c_int, [C.c_int, C.POINTER(vp)]),
             "np_ctx_destroy": (None, [vp]),
             "np_ctx_stream": (vp, [vp]),
@@ -374,6 +375,18 @@ class CodeParams:
 
     def __repr__(self):
         return f"CodeParams(n={self._n}, k={self._k}, wanted_n={self.wanted_n})"
+
+
+# enum np_kernel_family (include/novelpoly.h)
+FAMILY_GENERIC, FAMILY_SMALL, FAMILY_FAST, FAMILY_RES, FAMILY_BIG, FAMILY_HUGE = range(6)
+FAMILY_NAMES = ("GENERIC", "SMALL", "FAST", "RES", "BIG", "HUGE")
+
+
+def kernel_family(params: CodeParams, shard_len: int, reconstruct: bool) -> int:
+    """np_kernel_family: the kernel family (FAMILY_*) an encode, or with
+    `reconstruct` a reconstruct, of rows of `shard_len` bytes runs on in this
+    process; -1 for invalid parameters.  Needs no device."""
+    return int(lib().np_kernel_family(C.byref(params._c()), shard_len, 1 if reconstruct else 0))
 
 
 class ReedSolomon:

@@ -63,6 +63,35 @@ def test_huge_reconstruct(gpu, oracle, nw, kw, plen, erase):
     assert got[:plen] == pl
 
 
+# Explicit n = 2k (derive_parameters never gives it above k = 2048): the NQ = 2
+# instances at M = 8 and 16 sub-transforms per segment, a full 64-column tile
+# plus two columns with an odd payload tail, and three columns.
+N2K = [(n, k, plen) for n, k in ((16384, 8192), (32768, 16384)) for plen in (2 * k * 66 + 1, 2 * k * 3)]
+
+
+@pytest.mark.parametrize("n,k,plen", N2K)
+def test_huge_n_equals_2k(gpu, oracle, n, k, plen):
+    """The encode against the oracle, then the decode with k random erasures
+    (exactly k rows left) and with every systematic row lost."""
+    p = npa.CodeParams.derive_parameters(n, k)
+    assert (p.n(), p.k()) == (n, k)
+    sl = p.make_encoder(gpu).shard_len(plen)
+    assert (npa.kernel_family(p, sl, False), npa.kernel_family(p, sl, True)) == (npa.FAMILY_HUGE, npa.FAMILY_HUGE)
+    pl = synth.payload(n + plen, plen)
+    shards = p.make_encoder(gpu).encode(pl)
+    st, want = oracle.encode(pl, n, k, n)
+    assert st == 0
+    bad = [v for v in range(n) if shards[v] != want[v]]
+    assert not bad, f"{len(bad)} shards differ, first {bad[:5]}"
+    for gone in (set(synth.erasure_indices(plen + k, n, k).tolist()), set(range(k))):
+        recv = [None if i in gone else s for i, s in enumerate(shards)]
+        assert sum(r is not None for r in recv) == k
+        got = p.make_encoder(gpu).reconstruct(recv)
+        st, want_rec = oracle.reconstruct(recv, n, k)
+        assert st == 0 and got == want_rec
+        assert got[:plen] == pl
+
+
 # k = 16384 payloads of at most 32 columns: the sub-transform encode packs two
 # payloads into one 64-column tile (kernels_huge.hip HugeArgs::pair): odd and
 # even batches (the last tile half empty), whole and partial 32-column halves,

@@ -847,13 +847,23 @@ def test_host_pipeline_all_systematic_switched(gpu, env, nw, kw, plen):
 # any k >= 1, mod.rs:43-61; encode(bytes, n) never derives them): the encode
 # runs the specialised kernels (k = 256: kernels_fast.hip; k = 512 / 1024:
 # kernels_big.hip, their only route there), the reconstruct the generic kernels.
+# k = 256 at n = 65536: the generic decode at the largest n behind the fast
+# encode.  (65536, 32768): above the sub-transform kernels' k <= 16384, the
+# generic kernels in both directions (one column per workgroup, 128 KiB of
+# LDS), with exactly k rows left and with every systematic row lost.
 @pytest.mark.parametrize("nw,kw,plen,erase", [(4096, 256, 512 * 40 + 3, 3000), (8192, 512, 1024 * 9 + 1, 7000),
                                               (16384, 512, 1024 * 5, 15000), (16384, 1024, 2048 * 5 + 7, 14000),
-                                              (32768, 1024, 2048 * 3, 30000), (8192, 512, 1024 * 4, -1)])
+                                              (32768, 1024, 2048 * 3, 30000), (8192, 512, 1024 * 4, -1),
+                                              (65536, 32768, 2 * 32768 * 3 + 1, 32768),
+                                              (65536, 32768, 2 * 32768 * 3 + 1, -1), (65536, 256, 512 * 3 + 1, 65000)])
 def test_explicit_wide_codes(gpu, oracle, nw, kw, plen, erase):
     p = npa.CodeParams.derive_parameters(nw, kw)
     n, k = p.n(), p.k()
-    assert n // k >= 16 and (n, k) == (nw, kw)
+    assert (n, k) == (nw, kw)
+    sl = p.make_encoder(gpu).shard_len(plen)
+    enc_family = {256: npa.FAMILY_FAST, 512: npa.FAMILY_BIG, 1024: npa.FAMILY_BIG, 32768: npa.FAMILY_GENERIC}[k]
+    assert npa.kernel_family(p, sl, False) == enc_family and npa.kernel_family(p, sl, True) == npa.FAMILY_GENERIC
+    assert n // k >= 16 or k == 32768
     pl = synth.payload(nw + kw + plen, plen)
     shards = p.make_encoder(gpu).encode(pl)
     st, want = oracle.encode(pl, n, k, nw)
