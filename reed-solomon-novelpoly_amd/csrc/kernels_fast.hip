@@ -875,17 +875,50 @@ __device__ __forceinline__ void issue_rows(uint2 (&raw)[16], const uint8_t* sh, 
 // 2K-byte output columns (two 16-byte stores per column).  Full tiles with
 // 16-byte aligned output only; saves the LDS round trip and its two barriers.
 // (Streaming stores here cost +26 %: each wave writes a quarter of a line.)
-template <int K>
+// PAIR: lanes l and l + 32 first trade one 16-byte half per column
+// (v_permlane32_swap: the upper lanes of its first operand against the lower
+// lanes of its second), so that a store instruction has the pair writing the
+// two halves of one column's 32 bytes: 32 lines touched per instruction
+// instead of 64, for 16 swaps per wave and tile.  Config-3 decode -2 to -3 %
+// (profiles/r07/decode_phases_ab.txt).  Not where the next tile's rows are
+// live across the copy-out (kRowPrefetch): there it costs a spilled VGPR at
+// K = 256.
+template <int K, bool PAIR>
 __device__ __forceinline__ void copy_out_cq(uint8_t* out_tile, uint32_t lane, uint32_t g, const uint32_t (&L)[16],
                                             const uint32_t (&H)[16]) {
   uint2 d[4][4];
 #pragma unroll
   for (int u = 0; u < 4; ++u) cq_to_blks(&L[4 * u], &H[4 * u], d[u]);
+  if constexpr (PAIR) {
+    // afterwards d[0..1][i] hold bytes [0, 16) (in lane l) and [16, 32) (in
+    // lane l + 32) of lane l's column i, d[2..3][i] those of lane l + 32's
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    uint8_t* o = NP_BCHK(out_tile + static_cast<size_t>(4u * lane + i) * 2 * K + 32u * g, 32, kBkOut);
-    *reinterpret_cast<uint4*>(o) = make_uint4(d[0][i].x, d[0][i].y, d[1][i].x, d[1][i].y);
-    *reinterpret_cast<uint4*>(o + 16) = make_uint4(d[2][i].x, d[2][i].y, d[3][i].x, d[3][i].y);
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const auto x = __builtin_amdgcn_permlane32_swap(d[u][i].x, d[u + 2][i].x, false, false);
+        const auto y = __builtin_amdgcn_permlane32_swap(d[u][i].y, d[u + 2][i].y, false, false);
+        d[u][i] = make_uint2(x[0], y[0]);
+        d[u + 2][i] = make_uint2(x[1], y[1]);
+      }
+    }
+    // 32-bit lane offsets from the wave-uniform tile address (256 columns of
+    // 2K bytes): one address register per half of the columns
+    const uint32_t off = (lane & 31u) * (4u * 2 * K) + (lane >> 5) * 16u + 32u * g;
+    uint8_t* lo = out_tile + off;
+    uint8_t* up = out_tile + (off + 128u * 2 * K);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      *reinterpret_cast<uint4*>(NP_BCHK(lo + i * 2 * K, 16, kBkOut)) = make_uint4(d[0][i].x, d[0][i].y, d[1][i].x, d[1][i].y);
+      *reinterpret_cast<uint4*>(NP_BCHK(up + i * 2 * K, 16, kBkOut)) = make_uint4(d[2][i].x, d[2][i].y, d[3][i].x, d[3][i].y);
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      uint8_t* o = NP_BCHK(out_tile + static_cast<size_t>(4u * lane + i) * 2 * K + 32u * g, 32, kBkOut);
+      *reinterpret_cast<uint4*>(o) = make_uint4(d[0][i].x, d[0][i].y, d[1][i].x, d[1][i].y);
+      *reinterpret_cast<uint4*>(o + 16) = make_uint4(d[2][i].x, d[2][i].y, d[3][i].x, d[3][i].y);
+    }
   }
 }
 
@@ -1229,7 +1262,8 @@ __device__ __forceinline__ void rec_tile(const DevTables& T, const ReconstructAr
   }
   stamp(dbg, 30);
   if (full && out_vec_ok(a.out, a.out_stride)) {
-    copy_out_cq<K>(a.out + static_cast<size_t>(pb) * a.out_stride + static_cast<size_t>(col0) * 2 * K, lane, g, XL, XH);
+    copy_out_cq<K, !kRowPrefetch<NQ>>(
+        a.out + static_cast<size_t>(pb) * a.out_stride + static_cast<size_t>(col0) * 2 * K, lane, g, XL, XH);
     stamp(dbg, 31);
     return;
   }
@@ -1415,8 +1449,8 @@ __device__ __forceinline__ void rec_tiles(const DevTables& T, const ReconstructA
       }
     }
     if (full && out_vec_ok(a.out, a.out_stride)) {
-      copy_out_cq<K>(a.out + static_cast<size_t>(pb) * a.out_stride + static_cast<size_t>(col0) * 2 * K, lane, g, XL,
-                     XH);
+      copy_out_cq<K, !kRowPrefetch<NQ>>(
+          a.out + static_cast<size_t>(pb) * a.out_stride + static_cast<size_t>(col0) * 2 * K, lane, g, XL, XH);
       stamp(dbg, 31);
       continue;
     }
