@@ -1706,8 +1706,7 @@ struct MaskedShape {
 
 // own_payload: the decode goes to context scratch; both: the plan of a call that
 // restores and verifies (np::recover_plan_words).
-MaskedShape masked_shape(const np_ctx* c, const np_code_params* p, size_t shard_len, bool own_payload = true,
-                         bool both = false) {
+MaskedShape masked_shape(const np_ctx* c, const np_code_params* p, size_t shard_len, bool own_payload, bool both) {
   MaskedShape m{};
   m.n = static_cast<uint32_t>(p->n), m.k = static_cast<uint32_t>(p->k), m.wanted_n = static_cast<uint32_t>(p->wanted_n);
   m.direct = np::masked_encode_supported(m.n, m.k);
@@ -1744,8 +1743,8 @@ struct MaskedSlice {
 // without d_mismatch).
 hipError_t masked_reconstruct(np_ctx* c, const np_code_params* p, const MaskedShape& m, const uint8_t* d_shards,
                               size_t shard_len, size_t bstride, const uint8_t* d_present, size_t b0, size_t batch,
-                              uint32_t* d_status, size_t own_flags, hipStream_t s, MaskedSlice* sl,
-                              uint8_t* d_out = nullptr, size_t out_stride = 0) {
+                              uint32_t* d_status, size_t own_flags, hipStream_t s, MaskedSlice* sl, uint8_t* d_out,
+                              size_t out_stride) {
   const size_t cnt = std::min(m.per, batch - b0), own_status = d_status ? 0 : kStatusBytes;
   const size_t o_rows = align256(cnt * m.scr_pay), o_plan = o_rows + align256(cnt * m.rows_len);
   const size_t o_status = o_plan + align256(cnt * m.plan_len), o_flags = o_status + align256(cnt * own_status);
@@ -1770,84 +1769,19 @@ hipError_t masked_done(np_ctx* c, hipStream_t s, hipError_t e) {
   return HIP(hipEventRecord(c->restore_done, s));
 }
 
-// np_restore_shards_batch_dev after validation: per slice of the batch, the
-// reconstruct into the payload scratch, then either the row-masked encode
-// straight into d_shards or the unchanged encode into scratch rows and the
-// copy of the absent ones.  Caller holds the context lock.
-hipError_t launch_restore(np_ctx* c, const np_code_params* p, uint8_t* d_shards, size_t shard_len, size_t bstride,
-                          const uint8_t* d_present, size_t batch, uint32_t* d_status, hipStream_t s) {
-  const MaskedShape m = masked_shape(c, p, shard_len);
-  for (size_t b0 = 0; b0 < batch; b0 += m.per) {
-    MaskedSlice sl;
-    hipError_t e = masked_reconstruct(c, p, m, d_shards, shard_len, bstride, d_present, b0, batch, d_status, 0, s, &sl);
-    uint8_t* shards = d_shards + b0 * bstride;
-    if (e == hipSuccess && m.wanted_n) {
-      if (m.direct) {
-        e = HIP(np::launch_restore_plan(sl.a.present, sl.a.status, m.n, m.k, m.wanted_n, sl.cnt, sl.plan, s));
-        if (e == hipSuccess)
-          e = HIP(np::launch_encode_masked(c->T, enc_args(p, sl.scr, m.pay_len, m.pay_len, sl.cnt, shards, bstride),
-                                           sl.plan, s));
-      } else {
-        e = launch_encode(c, enc_args(p, sl.scr, m.pay_len, m.pay_len, sl.cnt, sl.rows, m.rows_len), s);
-        if (e == hipSuccess)
-          e = HIP(np::launch_copy_absent_rows(sl.rows, m.rows_len, shards, bstride, shard_len, sl.a.present,
-                                              sl.a.status, m.n, m.wanted_n, sl.cnt, s));
-      }
-    }
-    e = masked_done(c, s, e);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
-// np_verify_shards_batch_dev after validation: launch_restore's flow with a
-// compare in place of the store.  Per slice of the batch: the reconstruct into
-// the payload scratch, the flag map zeroed, then either the verify encode that
-// compares the present rows in [k, wanted_n) with d_shards as it produces them
-// or the unchanged encode into scratch rows and the compare of those rows, and
-// the count of the flags.  Shares the restore's scratch, ordering and cap.
-// Caller holds the context lock.
-hipError_t launch_verify(np_ctx* c, const np_code_params* p, const uint8_t* d_shards, size_t shard_len,
-                         size_t bstride, const uint8_t* d_present, size_t batch, uint32_t* d_bad_rows,
-                         uint8_t* d_mismatch, uint32_t* d_status, hipStream_t s) {
-  const MaskedShape m = masked_shape(c, p, shard_len);
-  for (size_t b0 = 0; b0 < batch; b0 += m.per) {
-    MaskedSlice sl;
-    hipError_t e = masked_reconstruct(c, p, m, d_shards, shard_len, bstride, d_present, b0, batch, d_status,
-                                      d_mismatch ? 0 : p->n, s, &sl);
-    const uint8_t* shards = d_shards + b0 * bstride;
-    uint8_t* flags = d_mismatch ? d_mismatch + b0 * p->n : sl.flags;
-    if (e == hipSuccess) e = HIP(hipMemsetAsync(flags, 0, sl.cnt * p->n, s));
-    if (e == hipSuccess && m.wanted_n > m.k) {
-      if (m.direct) {
-        e = HIP(np::launch_verify_plan(sl.a.present, sl.a.status, m.n, m.k, m.wanted_n, sl.cnt, sl.plan, s));
-        // (EncodeArgs names the rows as the encode's output; the verify encode only reads them)
-        if (e == hipSuccess)
-          e = HIP(np::launch_encode_verify(
-              c->T, enc_args(p, sl.scr, m.pay_len, m.pay_len, sl.cnt, const_cast<uint8_t*>(shards), bstride), sl.plan,
-              flags, s));
-      } else {
-        e = launch_encode(c, enc_args(p, sl.scr, m.pay_len, m.pay_len, sl.cnt, sl.rows, m.rows_len), s);
-        if (e == hipSuccess)
-          e = HIP(np::launch_compare_present_rows(sl.rows, m.rows_len, shards, bstride, shard_len, sl.a.present,
-                                                  sl.a.status, m.n, m.k, m.wanted_n, sl.cnt, flags, s));
-      }
-    }
-    if (e == hipSuccess) e = HIP(np::launch_verify_summary(flags, sl.a.status, m.n, sl.cnt, d_bad_rows + b0, s));
-    e = masked_done(c, s, e);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
-// np_recover_batch_dev after validation: what launch_restore and launch_verify
-// do, and the payload, from one reconstruct per slice.  With d_out the decode
-// goes straight to the caller's buffer, which is then the encode's payload
-// source: no payload scratch, and a direct shape runs unsliced.  A direct shape
-// with one request runs that request's plan and encode unchanged; with both, one
-// plan (np::launch_recover_plan) and one encode that stores the absent rows and
-// compares the present ones.  Every other shape encodes into scratch rows once
-// and copies and / or compares from them.  Caller holds the context lock.
+// np_recover_batch_dev after validation, and np_restore_shards_batch_dev and
+// np_verify_shards_batch_dev as its calls with one request and no d_out.  Per
+// slice of the batch: one reconstruct, into the payload scratch or, with d_out,
+// straight to the caller's buffer, which is then the encode's payload source
+// (no payload scratch, and a direct shape runs unsliced); for a verify the flag
+// map zeroed; the encode; for a verify the count of the flags.  A direct shape
+// runs the plan of its requests (np::launch_masked_plan) and one row-masked
+// encode: the restore's stores the absent rows straight into d_shards, the
+// verify's compares the present rows in [k, wanted_n) with d_shards as it
+// produces them, and with both requests one encode does both.  Every other
+// shape runs the unchanged encode into scratch rows once and copies the absent
+// rows and / or compares the present ones from them.  All share the restore
+// scratch, its ordering and its cap.  Caller holds the context lock.
 hipError_t launch_recover(np_ctx* c, const np_code_params* p, uint8_t* d_shards, size_t shard_len, size_t bstride,
                           const uint8_t* d_present, size_t batch, uint8_t* d_out, size_t out_stride, bool restore,
                           uint32_t* d_bad_rows, uint8_t* d_mismatch, uint32_t* d_status, hipStream_t s) {
@@ -1858,6 +1792,7 @@ hipError_t launch_recover(np_ctx* c, const np_code_params* p, uint8_t* d_shards,
   // the encode runs when a request has a row it can name: the restore any row
   // below wanted_n, the verify those in [k, wanted_n)
   const bool do_restore = restore && m.wanted_n, do_verify = verify && m.wanted_n > m.k;
+  const np::PlanKind kind = restore && verify ? np::kPlanRecover : restore ? np::kPlanAbsent : np::kPlanPresent;
   for (size_t b0 = 0; b0 < batch; b0 += m.per) {
     MaskedSlice sl;
     hipError_t e = masked_reconstruct(c, p, m, d_shards, shard_len, bstride, d_present, b0, batch, d_status,
@@ -1868,16 +1803,12 @@ hipError_t launch_recover(np_ctx* c, const np_code_params* p, uint8_t* d_shards,
     if (e == hipSuccess && (do_restore || do_verify)) {
       if (m.direct) {
         const np::EncodeArgs ea = enc_args(p, sl.pay, m.pay_len, sl.pay_stride, sl.cnt, shards, bstride);
-        if (restore && verify) {
-          e = HIP(np::launch_recover_plan(sl.a.present, sl.a.status, m.n, m.k, m.wanted_n, sl.cnt, sl.plan, s));
-          if (e == hipSuccess) e = HIP(np::launch_encode_recover(c->T, ea, sl.plan, flags, s));
-        } else if (restore) {
-          e = HIP(np::launch_restore_plan(sl.a.present, sl.a.status, m.n, m.k, m.wanted_n, sl.cnt, sl.plan, s));
-          if (e == hipSuccess) e = HIP(np::launch_encode_masked(c->T, ea, sl.plan, s));
-        } else {  // (do_verify; the verify encode only reads the rows)
-          e = HIP(np::launch_verify_plan(sl.a.present, sl.a.status, m.n, m.k, m.wanted_n, sl.cnt, sl.plan, s));
-          if (e == hipSuccess) e = HIP(np::launch_encode_verify(c->T, ea, sl.plan, flags, s));
-        }
+        e = HIP(np::launch_masked_plan(kind, sl.a.present, sl.a.status, m.n, m.k, m.wanted_n, sl.cnt, sl.plan, s));
+        // (EncodeArgs names the rows as the encode's output; the verify encode only reads them)
+        if (e == hipSuccess)
+          e = kind == np::kPlanRecover  ? HIP(np::launch_encode_recover(c->T, ea, sl.plan, flags, s))
+              : kind == np::kPlanAbsent ? HIP(np::launch_encode_masked(c->T, ea, sl.plan, s))
+                                        : HIP(np::launch_encode_verify(c->T, ea, sl.plan, flags, s));
       } else {
         e = launch_encode(c, enc_args(p, sl.pay, m.pay_len, sl.pay_stride, sl.cnt, sl.rows, m.rows_len), s);
         if (e == hipSuccess && do_restore)
@@ -1893,6 +1824,99 @@ hipError_t launch_recover(np_ctx* c, const np_code_params* p, uint8_t* d_shards,
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+// What a single-shot host call (np_rs_reconstruct, np_rs_restore_shards,
+// np_rs_verify_shards, np_rs_recover) received, as the crate validates it.
+struct Received {
+  std::vector<uint8_t> present;  // n flags
+  size_t have = 0, syms = 0;     // present shards; symbols per shard
+};
+
+int rs_received(const np_code_params* p, const uint8_t* const* shards, const size_t* lens, size_t n_received,
+                Received* r) {
+  if (!is_pow2(p->n) && !is_pow2(p->k)) return fail(NP_ERR_PARAMETER_MUST_BE_POWER_OF_2, p->n, p->k);
+  const size_t n = p->n, k = p->k;
+  // mod.rs:163-180: pad/truncate to n, erasures, existential count
+  r->present.assign(n, 0);
+  for (size_t i = 0; i < n && i < n_received; ++i) {
+    r->present[i] = shards[i] ? 1 : 0;
+    r->have += r->present[i];
+  }
+  if (r->have < k) return fail(NP_ERR_NEED_MORE_SHARDS, r->have, k, n);
+  // mod.rs:183-214: shard length from the first present shard
+  size_t first = 0;
+  while (!r->present[first]) ++first;
+  r->syms = (lens[first] + 1) / 2;
+  if (r->syms == 0) return fail(NP_ERR_EMPTY_SHARD);
+  for (size_t i = first + 1; i < n; ++i)
+    if (r->present[i] && (lens[i] + 1) / 2 != r->syms)
+      return fail(NP_ERR_INCONSISTENT_SHARD_LENGTHS, r->syms, (lens[i] + 1) / 2);
+  return check_params(p);
+}
+
+// The single-shot host calls after their argument checks: the received rows,
+// zero-padded, and the present mask through pinned staging, launch_recover for
+// a batch of one, and back whatever was asked for -- the payload (`out`), the
+// absent rows below wanted_n (`restored`), the count of mismatching rows and
+// their map (`bad_rows`, `mismatch`).  With `out` alone that is
+// launch_reconstruct and the payload's bytes.
+int rs_recover_one(np_ctx* c, const np_code_params* p, const uint8_t* const* shards, const size_t* lens,
+                   const Received& r, uint8_t* out, size_t* out_len, uint8_t* const* restored, size_t* bad_rows,
+                   uint8_t* mismatch) {
+  const size_t n = p->n, sl = 2 * r.syms, need = sl * p->k;
+  std::lock_guard<std::mutex> g(c->mu);
+  (void)hipSetDevice(c->device);
+  // results, as far as asked for: the payload, then (256-aligned) the count, then (256 bytes on) the n flags
+  const size_t o_cnt = !out ? 0 : bad_rows ? align256(need) : need, o_map = o_cnt + 256;
+  const size_t res_bytes = bad_rows ? o_map + n : o_cnt;
+  hipError_t e = HIP(c->h_in.ensure(n * sl));
+  if (e == hipSuccess) e = HIP(c->d_in.ensure(n * sl));
+  if (e == hipSuccess) e = HIP(c->d_present.ensure(n));
+  if (e == hipSuccess) e = HIP(c->h_pres.ensure(n));
+  if (e == hipSuccess) e = HIP(c->d_out.ensure(res_bytes));
+  if (e == hipSuccess) e = HIP(c->h_out.ensure(res_bytes));
+  if (e != hipSuccess) return dev_err(e);
+  std::memcpy(c->h_pres.p, r.present.data(), n);
+  uint8_t* stage = c->h_in.as<uint8_t>();
+  for (size_t i = 0; i < n; ++i) {
+    uint8_t* row = stage + i * sl;
+    if (r.present[i]) {
+      std::memcpy(row, shards[i], lens[i]);
+      if (lens[i] < sl) std::memset(row + lens[i], 0, sl - lens[i]);  // WrappedShard zero pad
+    } else {
+      std::memset(row, 0, sl);
+    }
+  }
+  hipStream_t s = c->stream;
+  uint8_t* d_res = c->d_out.as<uint8_t>();
+  e = HIP(hipMemcpyAsync(c->d_in.p, stage, n * sl, hipMemcpyHostToDevice, s));
+  if (e == hipSuccess) e = HIP(hipMemcpyAsync(c->d_present.p, c->h_pres.p, n, hipMemcpyHostToDevice, s));
+  if (e == hipSuccess)
+    e = launch_recover(c, p, c->d_in.as<uint8_t>(), sl, n * sl, c->d_present.as<uint8_t>(), 1, out ? d_res : nullptr,
+                       need, restored != nullptr, bad_rows ? reinterpret_cast<uint32_t*>(d_res + o_cnt) : nullptr,
+                       bad_rows ? d_res + o_map : nullptr, nullptr, s);
+  if (e == hipSuccess && res_bytes) e = HIP(hipMemcpyAsync(c->h_out.p, d_res, res_bytes, hipMemcpyDeviceToHost, s));
+  // the rows come back through the same pinned staging (the received ones unchanged)
+  if (e == hipSuccess && restored) e = HIP(hipMemcpyAsync(stage, c->d_in.p, p->wanted_n * sl, hipMemcpyDeviceToHost, s));
+  if (e == hipSuccess) e = HIP(hipStreamSynchronize(s));
+  if (e != hipSuccess) return dev_err(e);
+  const uint8_t* res = c->h_out.as<uint8_t>();
+  if (bad_rows) {
+    uint32_t count = 0;
+    std::memcpy(&count, res + o_cnt, sizeof(count));
+    if (count == UINT32_MAX) return fail(NP_ERR_NEED_MORE_SHARDS, r.have, p->k, n);  // (caught above: have >= k decodes)
+    *bad_rows = count;
+    if (mismatch) std::memcpy(mismatch, res + o_map, n);
+  }
+  if (out) {
+    std::memcpy(out, res, need);
+    *out_len = need;
+  }
+  if (restored)
+    for (size_t i = 0; i < p->wanted_n; ++i)
+      if (!r.present[i] && restored[i]) std::memcpy(restored[i], stage + i * sl, sl);
+  return NP_OK;
 }
 
 }  // namespace
@@ -1925,8 +1949,9 @@ int np_verify_shards_batch_dev(np_ctx* c, const np_code_params* p, const uint8_t
   if (!d_shards || !d_present || !d_bad_rows || bstride < p->n * shard_len) return fail(NP_ERR_INVALID_ARGUMENT);
   std::lock_guard<std::mutex> g(c->mu);  // context scratch
   (void)hipSetDevice(c->device);
-  return dev_err(launch_verify(c, p, d_shards, shard_len, bstride, d_present, batch, d_bad_rows, d_mismatch,
-                               reinterpret_cast<uint32_t*>(d_status), pick(c, stream)));
+  // (a verify writes no shard row)
+  return dev_err(launch_recover(c, p, const_cast<uint8_t*>(d_shards), shard_len, bstride, d_present, batch, nullptr, 0,
+                                false, d_bad_rows, d_mismatch, reinterpret_cast<uint32_t*>(d_status), pick(c, stream)));
 }
 
 int np_restore_shards_batch_dev(np_ctx* c, const np_code_params* p, uint8_t* d_shards, size_t shard_len,
@@ -1939,8 +1964,8 @@ int np_restore_shards_batch_dev(np_ctx* c, const np_code_params* p, uint8_t* d_s
   if (!d_shards || !d_present || bstride < p->n * shard_len) return fail(NP_ERR_INVALID_ARGUMENT);
   std::lock_guard<std::mutex> g(c->mu);  // context scratch
   (void)hipSetDevice(c->device);
-  return dev_err(launch_restore(c, p, d_shards, shard_len, bstride, d_present, batch,
-                                reinterpret_cast<uint32_t*>(d_status), pick(c, stream)));
+  return dev_err(launch_recover(c, p, d_shards, shard_len, bstride, d_present, batch, nullptr, 0, true, nullptr,
+                                nullptr, reinterpret_cast<uint32_t*>(d_status), pick(c, stream)));
 }
 
 int np_reconstruct_batch_dev3(np_ctx* c, const np_code_params* p, const uint8_t* d_shards, size_t shard_len,
@@ -2002,269 +2027,46 @@ int np_reconstruct_batch_dev(np_ctx* c, const np_code_params* p, const uint8_t* 
 int np_rs_reconstruct(np_ctx* c, const np_code_params* p, const uint8_t* const* shards, const size_t* lens,
                       size_t n_received, uint8_t* out, size_t cap, size_t* out_len) {
   if (!c || !p || (n_received && (!shards || !lens))) return fail(NP_ERR_INVALID_ARGUMENT);
-  if (!is_pow2(p->n) && !is_pow2(p->k)) return fail(NP_ERR_PARAMETER_MUST_BE_POWER_OF_2, p->n, p->k);
-  const size_t n = p->n, k = p->k;
-  // mod.rs:163-180: pad/truncate to n, erasures, existential count
-  std::vector<uint8_t> present(n, 0);
-  size_t have = 0;
-  for (size_t i = 0; i < n && i < n_received; ++i) {
-    present[i] = shards[i] ? 1 : 0;
-    have += present[i];
-  }
-  if (have < k) return fail(NP_ERR_NEED_MORE_SHARDS, have, k, n);
-  // mod.rs:183-214: shard length from the first present shard
-  size_t first = 0;
-  while (!present[first]) ++first;
-  const size_t syms = (lens[first] + 1) / 2;
-  if (syms == 0) return fail(NP_ERR_EMPTY_SHARD);
-  for (size_t i = first + 1; i < n; ++i)
-    if (present[i] && (lens[i] + 1) / 2 != syms) return fail(NP_ERR_INCONSISTENT_SHARD_LENGTHS, syms, (lens[i] + 1) / 2);
-  int st = check_params(p);
+  Received r;
+  int st = rs_received(p, shards, lens, n_received, &r);
   if (st) return st;
-  const size_t need = syms * 2 * k;
+  const size_t need = r.syms * 2 * p->k;
   if (!out || !out_len || cap < need) return fail(NP_ERR_INVALID_ARGUMENT, need);
-  const size_t sl = 2 * syms;
-  std::lock_guard<std::mutex> g(c->mu);
-  (void)hipSetDevice(c->device);
-  hipError_t e = HIP(c->h_in.ensure(n * sl));
-  if (e == hipSuccess) e = HIP(c->d_in.ensure(n * sl));
-  if (e == hipSuccess) e = HIP(c->d_out.ensure(need));
-  if (e == hipSuccess) e = HIP(c->h_out.ensure(need));
-  if (e == hipSuccess) e = HIP(c->d_present.ensure(n));
-  if (e == hipSuccess) e = HIP(c->h_pres.ensure(n));
-  if (e != hipSuccess) return dev_err(e);
-  std::memcpy(c->h_pres.p, present.data(), n);
-  uint8_t* stage = c->h_in.as<uint8_t>();
-  for (size_t i = 0; i < n; ++i) {
-    uint8_t* row = stage + i * sl;
-    if (present[i]) {
-      std::memcpy(row, shards[i], lens[i]);
-      if (lens[i] < sl) std::memset(row + lens[i], 0, sl - lens[i]);  // WrappedShard zero pad
-    } else {
-      std::memset(row, 0, sl);
-    }
-  }
-  hipStream_t s = c->stream;
-  e = HIP(hipMemcpyAsync(c->d_in.p, stage, n * sl, hipMemcpyHostToDevice, s));
-  if (e == hipSuccess) e = HIP(hipMemcpyAsync(c->d_present.p, c->h_pres.p, n, hipMemcpyHostToDevice, s));
-  if (e == hipSuccess) {
-    np::ReconstructArgs a{};
-    a.shards = c->d_in.as<uint8_t>();
-    a.shard_len = sl;
-    a.batch_stride = n * sl;
-    a.present = c->d_present.as<uint8_t>();
-    a.locators = nullptr;  // computed on the device
-    a.batch = 1;
-    a.n = static_cast<uint32_t>(n);
-    a.k = static_cast<uint32_t>(k);
-    a.out = c->d_out.as<uint8_t>();
-    a.out_stride = need;
-    e = HIP(launch_reconstruct(c, a, s));
-  }
-  if (e == hipSuccess) e = HIP(hipMemcpyAsync(c->h_out.p, c->d_out.p, need, hipMemcpyDeviceToHost, s));
-  if (e == hipSuccess) e = HIP(hipStreamSynchronize(s));
-  if (e != hipSuccess) return dev_err(e);
-  std::memcpy(out, c->h_out.p, need);
-  *out_len = need;
-  return NP_OK;
+  return rs_recover_one(c, p, shards, lens, r, out, out_len, nullptr, nullptr, nullptr);
 }
 
 int np_rs_restore_shards(np_ctx* c, const np_code_params* p, const uint8_t* const* shards, const size_t* lens,
                          size_t n_received, uint8_t* const* restored, size_t restored_len) {
-  // validation as np_rs_reconstruct (mod.rs:163-214)
   if (!c || !p || (n_received && (!shards || !lens))) return fail(NP_ERR_INVALID_ARGUMENT);
-  if (!is_pow2(p->n) && !is_pow2(p->k)) return fail(NP_ERR_PARAMETER_MUST_BE_POWER_OF_2, p->n, p->k);
-  const size_t n = p->n, k = p->k;
-  std::vector<uint8_t> present(n, 0);
-  size_t have = 0;
-  for (size_t i = 0; i < n && i < n_received; ++i) {
-    present[i] = shards[i] ? 1 : 0;
-    have += present[i];
-  }
-  if (have < k) return fail(NP_ERR_NEED_MORE_SHARDS, have, k, n);
-  size_t first = 0;
-  while (!present[first]) ++first;
-  const size_t syms = (lens[first] + 1) / 2;
-  if (syms == 0) return fail(NP_ERR_EMPTY_SHARD);
-  for (size_t i = first + 1; i < n; ++i)
-    if (present[i] && (lens[i] + 1) / 2 != syms) return fail(NP_ERR_INCONSISTENT_SHARD_LENGTHS, syms, (lens[i] + 1) / 2);
-  int st = check_params(p);
+  Received r;
+  int st = rs_received(p, shards, lens, n_received, &r);
   if (st) return st;
-  const size_t sl = 2 * syms;
+  const size_t sl = 2 * r.syms;
   if (!restored || restored_len < sl) return fail(NP_ERR_INVALID_ARGUMENT, sl);
-  std::lock_guard<std::mutex> g(c->mu);
-  (void)hipSetDevice(c->device);
-  hipError_t e = HIP(c->h_in.ensure(n * sl));
-  if (e == hipSuccess) e = HIP(c->d_in.ensure(n * sl));
-  if (e == hipSuccess) e = HIP(c->d_present.ensure(n));
-  if (e == hipSuccess) e = HIP(c->h_pres.ensure(n));
-  if (e != hipSuccess) return dev_err(e);
-  std::memcpy(c->h_pres.p, present.data(), n);
-  uint8_t* stage = c->h_in.as<uint8_t>();
-  for (size_t i = 0; i < n; ++i) {
-    uint8_t* row = stage + i * sl;
-    if (present[i]) {
-      std::memcpy(row, shards[i], lens[i]);
-      if (lens[i] < sl) std::memset(row + lens[i], 0, sl - lens[i]);  // WrappedShard zero pad
-    } else {
-      std::memset(row, 0, sl);
-    }
-  }
-  hipStream_t s = c->stream;
-  e = HIP(hipMemcpyAsync(c->d_in.p, stage, n * sl, hipMemcpyHostToDevice, s));
-  if (e == hipSuccess) e = HIP(hipMemcpyAsync(c->d_present.p, c->h_pres.p, n, hipMemcpyHostToDevice, s));
-  if (e == hipSuccess)
-    e = launch_restore(c, p, c->d_in.as<uint8_t>(), sl, n * sl, c->d_present.as<uint8_t>(), 1, nullptr, s);
-  // the rows come back through the same pinned staging (the received ones unchanged)
-  if (e == hipSuccess) e = HIP(hipMemcpyAsync(stage, c->d_in.p, p->wanted_n * sl, hipMemcpyDeviceToHost, s));
-  if (e == hipSuccess) e = HIP(hipStreamSynchronize(s));
-  if (e != hipSuccess) return dev_err(e);
-  for (size_t i = 0; i < p->wanted_n; ++i)
-    if (!present[i] && restored[i]) std::memcpy(restored[i], stage + i * sl, sl);
-  return NP_OK;
+  return rs_recover_one(c, p, shards, lens, r, nullptr, nullptr, restored, nullptr, nullptr);
 }
 
 int np_rs_verify_shards(np_ctx* c, const np_code_params* p, const uint8_t* const* shards, const size_t* lens,
                         size_t n_received, size_t* bad_rows, uint8_t* mismatch) {
-  // validation as np_rs_reconstruct (mod.rs:163-214)
   if (!c || !p || !bad_rows || (n_received && (!shards || !lens))) return fail(NP_ERR_INVALID_ARGUMENT);
-  if (!is_pow2(p->n) && !is_pow2(p->k)) return fail(NP_ERR_PARAMETER_MUST_BE_POWER_OF_2, p->n, p->k);
-  const size_t n = p->n, k = p->k;
-  std::vector<uint8_t> present(n, 0);
-  size_t have = 0;
-  for (size_t i = 0; i < n && i < n_received; ++i) {
-    present[i] = shards[i] ? 1 : 0;
-    have += present[i];
-  }
-  if (have < k) return fail(NP_ERR_NEED_MORE_SHARDS, have, k, n);
-  size_t first = 0;
-  while (!present[first]) ++first;
-  const size_t syms = (lens[first] + 1) / 2;
-  if (syms == 0) return fail(NP_ERR_EMPTY_SHARD);
-  for (size_t i = first + 1; i < n; ++i)
-    if (present[i] && (lens[i] + 1) / 2 != syms) return fail(NP_ERR_INCONSISTENT_SHARD_LENGTHS, syms, (lens[i] + 1) / 2);
-  int st = check_params(p);
+  Received r;
+  int st = rs_received(p, shards, lens, n_received, &r);
   if (st) return st;
-  const size_t sl = 2 * syms;
-  std::lock_guard<std::mutex> g(c->mu);
-  (void)hipSetDevice(c->device);
-  // the count, then (256 bytes on) the n flags
-  const size_t o_map = 256, res_bytes = o_map + n;
-  hipError_t e = HIP(c->h_in.ensure(n * sl));
-  if (e == hipSuccess) e = HIP(c->d_in.ensure(n * sl));
-  if (e == hipSuccess) e = HIP(c->d_present.ensure(n));
-  if (e == hipSuccess) e = HIP(c->h_pres.ensure(n));
-  if (e == hipSuccess) e = HIP(c->d_out.ensure(res_bytes));
-  if (e == hipSuccess) e = HIP(c->h_out.ensure(res_bytes));
-  if (e != hipSuccess) return dev_err(e);
-  std::memcpy(c->h_pres.p, present.data(), n);
-  uint8_t* stage = c->h_in.as<uint8_t>();
-  for (size_t i = 0; i < n; ++i) {
-    uint8_t* row = stage + i * sl;
-    if (present[i]) {
-      std::memcpy(row, shards[i], lens[i]);
-      if (lens[i] < sl) std::memset(row + lens[i], 0, sl - lens[i]);  // WrappedShard zero pad
-    } else {
-      std::memset(row, 0, sl);
-    }
-  }
-  hipStream_t s = c->stream;
-  uint8_t* d_res = c->d_out.as<uint8_t>();
-  e = HIP(hipMemcpyAsync(c->d_in.p, stage, n * sl, hipMemcpyHostToDevice, s));
-  if (e == hipSuccess) e = HIP(hipMemcpyAsync(c->d_present.p, c->h_pres.p, n, hipMemcpyHostToDevice, s));
-  if (e == hipSuccess)
-    e = launch_verify(c, p, c->d_in.as<uint8_t>(), sl, n * sl, c->d_present.as<uint8_t>(), 1,
-                      reinterpret_cast<uint32_t*>(d_res), d_res + o_map, nullptr, s);
-  if (e == hipSuccess) e = HIP(hipMemcpyAsync(c->h_out.p, d_res, res_bytes, hipMemcpyDeviceToHost, s));
-  if (e == hipSuccess) e = HIP(hipStreamSynchronize(s));
-  if (e != hipSuccess) return dev_err(e);
-  const uint8_t* res = c->h_out.as<uint8_t>();
-  uint32_t count = 0;
-  std::memcpy(&count, res, sizeof(count));
-  if (count == UINT32_MAX) return fail(NP_ERR_NEED_MORE_SHARDS, have, k, n);  // (caught above: have >= k decodes)
-  *bad_rows = count;
-  if (mismatch) std::memcpy(mismatch, res + o_map, n);
-  return NP_OK;
+  return rs_recover_one(c, p, shards, lens, r, nullptr, nullptr, nullptr, bad_rows, mismatch);
 }
 
 int np_rs_recover(np_ctx* c, const np_code_params* p, const uint8_t* const* shards, const size_t* lens,
                   size_t n_received, uint8_t* out, size_t cap, size_t* out_len, uint8_t* const* restored,
                   size_t restored_len, size_t* bad_rows, uint8_t* mismatch) {
-  // validation as np_rs_reconstruct (mod.rs:163-214)
   if (!c || !p || (n_received && (!shards || !lens))) return fail(NP_ERR_INVALID_ARGUMENT);
   if ((!out && !restored && !bad_rows) || (mismatch && !bad_rows)) return fail(NP_ERR_INVALID_ARGUMENT);
-  if (!is_pow2(p->n) && !is_pow2(p->k)) return fail(NP_ERR_PARAMETER_MUST_BE_POWER_OF_2, p->n, p->k);
-  const size_t n = p->n, k = p->k;
-  std::vector<uint8_t> present(n, 0);
-  size_t have = 0;
-  for (size_t i = 0; i < n && i < n_received; ++i) {
-    present[i] = shards[i] ? 1 : 0;
-    have += present[i];
-  }
-  if (have < k) return fail(NP_ERR_NEED_MORE_SHARDS, have, k, n);
-  size_t first = 0;
-  while (!present[first]) ++first;
-  const size_t syms = (lens[first] + 1) / 2;
-  if (syms == 0) return fail(NP_ERR_EMPTY_SHARD);
-  for (size_t i = first + 1; i < n; ++i)
-    if (present[i] && (lens[i] + 1) / 2 != syms) return fail(NP_ERR_INCONSISTENT_SHARD_LENGTHS, syms, (lens[i] + 1) / 2);
-  int st = check_params(p);
+  Received r;
+  int st = rs_received(p, shards, lens, n_received, &r);
   if (st) return st;
-  const size_t sl = 2 * syms, need = syms * 2 * k;
+  const size_t sl = 2 * r.syms, need = r.syms * 2 * p->k;
   if (out && (!out_len || cap < need)) return fail(NP_ERR_INVALID_ARGUMENT, need);
   if (restored && restored_len < sl) return fail(NP_ERR_INVALID_ARGUMENT, sl);
-  std::lock_guard<std::mutex> g(c->mu);
-  (void)hipSetDevice(c->device);
-  // results: the payload, then (256-aligned) the count, then (256 bytes on) the n flags
-  const size_t o_cnt = out ? align256(need) : 0, o_map = o_cnt + 256, res_bytes = o_map + n;
-  hipError_t e = HIP(c->h_in.ensure(n * sl));
-  if (e == hipSuccess) e = HIP(c->d_in.ensure(n * sl));
-  if (e == hipSuccess) e = HIP(c->d_present.ensure(n));
-  if (e == hipSuccess) e = HIP(c->h_pres.ensure(n));
-  if (e == hipSuccess) e = HIP(c->d_out.ensure(res_bytes));
-  if (e == hipSuccess) e = HIP(c->h_out.ensure(res_bytes));
-  if (e != hipSuccess) return dev_err(e);
-  std::memcpy(c->h_pres.p, present.data(), n);
-  uint8_t* stage = c->h_in.as<uint8_t>();
-  for (size_t i = 0; i < n; ++i) {
-    uint8_t* row = stage + i * sl;
-    if (present[i]) {
-      std::memcpy(row, shards[i], lens[i]);
-      if (lens[i] < sl) std::memset(row + lens[i], 0, sl - lens[i]);  // WrappedShard zero pad
-    } else {
-      std::memset(row, 0, sl);
-    }
-  }
-  hipStream_t s = c->stream;
-  uint8_t* d_res = c->d_out.as<uint8_t>();
-  e = HIP(hipMemcpyAsync(c->d_in.p, stage, n * sl, hipMemcpyHostToDevice, s));
-  if (e == hipSuccess) e = HIP(hipMemcpyAsync(c->d_present.p, c->h_pres.p, n, hipMemcpyHostToDevice, s));
-  if (e == hipSuccess)
-    e = launch_recover(c, p, c->d_in.as<uint8_t>(), sl, n * sl, c->d_present.as<uint8_t>(), 1, out ? d_res : nullptr,
-                       need, restored != nullptr, bad_rows ? reinterpret_cast<uint32_t*>(d_res + o_cnt) : nullptr,
-                       bad_rows ? d_res + o_map : nullptr, nullptr, s);
-  if (e == hipSuccess && (out || bad_rows))
-    e = HIP(hipMemcpyAsync(c->h_out.p, d_res, res_bytes, hipMemcpyDeviceToHost, s));
-  // the rows come back through the same pinned staging (the received ones unchanged)
-  if (e == hipSuccess && restored) e = HIP(hipMemcpyAsync(stage, c->d_in.p, p->wanted_n * sl, hipMemcpyDeviceToHost, s));
-  if (e == hipSuccess) e = HIP(hipStreamSynchronize(s));
-  if (e != hipSuccess) return dev_err(e);
-  const uint8_t* res = c->h_out.as<uint8_t>();
-  if (bad_rows) {
-    uint32_t count = 0;
-    std::memcpy(&count, res + o_cnt, sizeof(count));
-    if (count == UINT32_MAX) return fail(NP_ERR_NEED_MORE_SHARDS, have, k, n);  // (caught above: have >= k decodes)
-    *bad_rows = count;
-    if (mismatch) std::memcpy(mismatch, res + o_map, n);
-  }
-  if (out) {
-    std::memcpy(out, res, need);
-    *out_len = need;
-  }
-  if (restored)
-    for (size_t i = 0; i < p->wanted_n; ++i)
-      if (!present[i] && restored[i]) std::memcpy(restored[i], stage + i * sl, sl);
-  return NP_OK;
+  return rs_recover_one(c, p, shards, lens, r, out, out_len, restored, bad_rows, mismatch);
 }
 
 int np_reconstruct(np_ctx* c, const uint8_t* const* shards, const size_t* lens, size_t n_received,
@@ -2629,8 +2431,8 @@ int ragged_masked_validate(const np_code_params* p, const np_ragged_item* items,
   return NP_OK;
 }
 
-// The end of the run of items starting at b0 that one uniform restore / verify
-// serves: equal shard_len, shards_off advancing by one constant stride no
+// The end of the run of items starting at b0 that one uniform recover without
+// d_out serves: equal shard_len, shards_off advancing by one constant stride no
 // smaller than n * shard_len.  (ragged_run also breaks on the payload fields,
 // which these calls ignore.)
 size_t ragged_shard_run(const np_ragged_item* items, size_t b0, size_t batch, uint64_t rows, uint64_t* sstride) {
@@ -2651,8 +2453,9 @@ size_t ragged_shard_run(const np_ragged_item* items, size_t b0, size_t batch, ui
   return e;
 }
 
-// One slice of a direct ragged restore / verify: items [b0, b0 + cnt) decoded
-// into the restore scratch, with everything both masked launches share.
+// One slice of a direct ragged restore / verify / recover: items [b0, b0 + cnt)
+// decoded into the restore scratch or the caller's buffer, with everything the
+// masked launches share.
 struct RaggedMaskedSlice {
   size_t cnt = 0;
   uint8_t* scr = nullptr;  // the restore scratch: payloads, plan, status, flags
@@ -2685,7 +2488,7 @@ size_t ragged_masked_slice_end(const np_ctx* c, const np_code_params* p, const n
 hipError_t ragged_masked_reconstruct(np_ctx* c, const np_code_params* p, const uint8_t* d_shards, size_t shards_size,
                                      const uint8_t* d_present, const np_ragged_item* items, size_t b0, size_t cnt,
                                      uint32_t* d_status, size_t own_flags, hipStream_t s, RaggedMaskedSlice* sl,
-                                     bool both = false, uint8_t* d_out = nullptr, size_t out_size = 0) {
+                                     bool both, uint8_t* d_out, size_t out_size) {
   const uint32_t n = static_cast<uint32_t>(p->n), k = static_cast<uint32_t>(p->k);
   const size_t own_status = d_status ? 0 : kStatusBytes;
   const size_t stride = np::prefix_stride(n, k);
@@ -2740,88 +2543,6 @@ hipError_t ragged_masked_done(np_ctx* c, hipStream_t s, hipError_t e) {
   return masked_done(c, s, e);
 }
 
-// np_restore_shards_ragged_dev after validation.  Direct shapes, per slice: the
-// ragged reconstruct into the restore scratch, the restore plan of the slice's
-// items, and the ragged masked encode straight into d_shards on the same
-// records and block table.  Every other shape: runs of equally long items at a
-// constant spacing through launch_restore.  Caller holds the context lock.
-hipError_t launch_restore_ragged_all(np_ctx* c, const np_code_params* p, uint8_t* d_shards, size_t shards_size,
-                                     const uint8_t* d_present, const np_ragged_item* items, size_t batch,
-                                     uint32_t* d_status, hipStream_t s) {
-  const uint32_t n = static_cast<uint32_t>(p->n), k = static_cast<uint32_t>(p->k);
-  const uint32_t wanted_n = static_cast<uint32_t>(p->wanted_n);
-  if (np::ragged_masked_supported(n, k)) {
-    const size_t per = std::max<size_t>(1, c->big_cap / np::prefix_stride(n, k));
-    for (size_t b0 = 0; b0 < batch;) {
-      const size_t b1 = ragged_masked_slice_end(c, p, items, b0, batch, per);
-      RaggedMaskedSlice sl;
-      hipError_t e = ragged_masked_reconstruct(c, p, d_shards, shards_size, d_present, items, b0, b1 - b0, d_status, 0,
-                                               s, &sl);
-      if (e == hipSuccess && wanted_n) {
-        e = HIP(np::launch_restore_plan(sl.r.present, sl.r.status, n, k, wanted_n, sl.cnt, sl.plan, s));
-        if (e == hipSuccess) e = HIP(np::launch_encode_masked_ragged(c->T, sl.r, sl.plan, s));
-      }
-      e = ragged_masked_done(c, s, e);
-      if (e != hipSuccess) return e;
-      b0 = b1;
-    }
-    return hipSuccess;
-  }
-  for (size_t b0 = 0; b0 < batch;) {
-    uint64_t bstride = 0;
-    const size_t b1 = ragged_shard_run(items, b0, batch, p->n, &bstride);
-    const np_ragged_item& it = items[b0];
-    hipError_t e = launch_restore(c, p, d_shards + it.shards_off, it.shard_len, bstride, d_present + b0 * p->n,
-                                  b1 - b0, d_status ? d_status + 2 * b0 : nullptr, s);
-    if (e != hipSuccess) return e;
-    b0 = b1;
-  }
-  return hipSuccess;
-}
-
-// np_verify_shards_ragged_dev after validation: launch_restore_ragged_all's flow
-// with the flag map zeroed, the verify plan, the ragged verify encode and the
-// count of the flags.  Caller holds the context lock.
-hipError_t launch_verify_ragged_all(np_ctx* c, const np_code_params* p, const uint8_t* d_shards, size_t shards_size,
-                                    const uint8_t* d_present, const np_ragged_item* items, size_t batch,
-                                    uint32_t* d_bad_rows, uint8_t* d_mismatch, uint32_t* d_status, hipStream_t s) {
-  const uint32_t n = static_cast<uint32_t>(p->n), k = static_cast<uint32_t>(p->k);
-  const uint32_t wanted_n = static_cast<uint32_t>(p->wanted_n);
-  if (np::ragged_masked_supported(n, k)) {
-    const size_t per = std::max<size_t>(1, c->big_cap / np::prefix_stride(n, k));
-    for (size_t b0 = 0; b0 < batch;) {
-      const size_t b1 = ragged_masked_slice_end(c, p, items, b0, batch, per);
-      RaggedMaskedSlice sl;
-      hipError_t e = ragged_masked_reconstruct(c, p, d_shards, shards_size, d_present, items, b0, b1 - b0, d_status,
-                                               d_mismatch ? 0 : p->n, s, &sl);
-      if (e == hipSuccess) {
-        uint8_t* flags = d_mismatch ? d_mismatch + b0 * p->n : sl.scr + sl.o_flags;
-        e = HIP(hipMemsetAsync(flags, 0, sl.cnt * p->n, s));
-        if (e == hipSuccess && wanted_n > k) {
-          e = HIP(np::launch_verify_plan(sl.r.present, sl.r.status, n, k, wanted_n, sl.cnt, sl.plan, s));
-          if (e == hipSuccess) e = HIP(np::launch_encode_verify_ragged(c->T, sl.r, sl.plan, flags, s));
-        }
-        if (e == hipSuccess) e = HIP(np::launch_verify_summary(flags, sl.r.status, n, sl.cnt, d_bad_rows + b0, s));
-      }
-      e = ragged_masked_done(c, s, e);
-      if (e != hipSuccess) return e;
-      b0 = b1;
-    }
-    return hipSuccess;
-  }
-  for (size_t b0 = 0; b0 < batch;) {
-    uint64_t bstride = 0;
-    const size_t b1 = ragged_shard_run(items, b0, batch, p->n, &bstride);
-    const np_ragged_item& it = items[b0];
-    hipError_t e = launch_verify(c, p, d_shards + it.shards_off, it.shard_len, bstride, d_present + b0 * p->n, b1 - b0,
-                                 d_bad_rows + b0, d_mismatch ? d_mismatch + b0 * p->n : nullptr,
-                                 d_status ? d_status + 2 * b0 : nullptr, s);
-    if (e != hipSuccess) return e;
-    b0 = b1;
-  }
-  return hipSuccess;
-}
-
 // Items [b0, b0 + cnt) of a direct ragged recover with d_out, which keeps no
 // payload in scratch: the slice ends where the plan words, the own status and
 // the own flag rows (`small` bytes per item, three 256-aligned arrays) would
@@ -2831,14 +2552,17 @@ size_t ragged_recover_slice_end(const np_ctx* c, size_t b0, size_t batch, size_t
   return b0 + std::min(batch - b0, std::min(per_records, std::max<size_t>(1, room / small)));
 }
 
-// np_recover_ragged_dev after validation: what launch_restore_ragged_all and
-// launch_verify_ragged_all do, and the payload, from one ragged reconstruct per
-// slice.  With d_out the decode goes straight to the caller's
-// buffer, whose items are then the encode's payloads: no payload scratch.  A
-// direct shape with one request runs that request's plan and ragged encode
-// unchanged; with both, the recover plan and the ragged recover encode.  Every
-// other shape: runs of equally long items at constant spacings through
-// launch_recover.  Caller holds the context lock.
+// np_recover_ragged_dev after validation, and
+// np_restore_shards_ragged_dev and np_verify_shards_ragged_dev as its calls with
+// one request and no d_out.  Direct shapes, per slice: one ragged reconstruct,
+// into the restore scratch or, with d_out, straight to the caller's buffer,
+// whose items are then the encode's payloads (no payload scratch); for a verify
+// the flag map zeroed; the plan of the requests for the slice's items and one
+// ragged row-masked encode on the same records and block table (the restore's
+// stores straight into d_shards, the verify's compares, with both requests one
+// encode does both); for a verify the count of the flags.  Every other shape:
+// runs of equally long items at constant spacings through launch_recover.
+// Caller holds the context lock.
 hipError_t launch_recover_ragged_all(np_ctx* c, const np_code_params* p, uint8_t* d_shards, size_t shards_size,
                                      const uint8_t* d_present, uint8_t* d_out, size_t out_size,
                                      const np_ragged_item* items, size_t batch, bool restore, uint32_t* d_bad_rows,
@@ -2852,6 +2576,7 @@ hipError_t launch_recover_ragged_all(np_ctx* c, const np_code_params* p, uint8_t
   if (np::ragged_masked_supported(n, k)) {
     // (launch_recover's: the encode runs when a request has a row it can name)
     const bool both = restore && verify, do_restore = restore && wanted_n, do_verify = verify && wanted_n > k;
+    const np::PlanKind kind = both ? np::kPlanRecover : restore ? np::kPlanAbsent : np::kPlanPresent;
     const size_t own_flags = verify && !d_mismatch ? p->n : 0;
     const size_t small = (both ? np::recover_plan_words(n, k) : np::restore_plan_words(n, k)) * sizeof(uint32_t) +
                          (d_status ? 0 : kStatusBytes) + own_flags;
@@ -2865,16 +2590,11 @@ hipError_t launch_recover_ragged_all(np_ctx* c, const np_code_params* p, uint8_t
       uint8_t* flags = d_mismatch ? d_mismatch + b0 * p->n : sl.scr + sl.o_flags;
       if (e == hipSuccess && verify) e = HIP(hipMemsetAsync(flags, 0, sl.cnt * p->n, s));
       if (e == hipSuccess && (do_restore || do_verify)) {
-        if (both) {
-          e = HIP(np::launch_recover_plan(sl.r.present, sl.r.status, n, k, wanted_n, sl.cnt, sl.plan, s));
-          if (e == hipSuccess) e = HIP(np::launch_encode_recover_ragged(c->T, sl.r, sl.plan, flags, s));
-        } else if (restore) {
-          e = HIP(np::launch_restore_plan(sl.r.present, sl.r.status, n, k, wanted_n, sl.cnt, sl.plan, s));
-          if (e == hipSuccess) e = HIP(np::launch_encode_masked_ragged(c->T, sl.r, sl.plan, s));
-        } else {  // (do_verify; the verify encode only reads the rows)
-          e = HIP(np::launch_verify_plan(sl.r.present, sl.r.status, n, k, wanted_n, sl.cnt, sl.plan, s));
-          if (e == hipSuccess) e = HIP(np::launch_encode_verify_ragged(c->T, sl.r, sl.plan, flags, s));
-        }
+        e = HIP(np::launch_masked_plan(kind, sl.r.present, sl.r.status, n, k, wanted_n, sl.cnt, sl.plan, s));
+        if (e == hipSuccess)
+          e = both      ? HIP(np::launch_encode_recover_ragged(c->T, sl.r, sl.plan, flags, s))
+              : restore ? HIP(np::launch_encode_masked_ragged(c->T, sl.r, sl.plan, s))
+                        : HIP(np::launch_encode_verify_ragged(c->T, sl.r, sl.plan, flags, s));
       }
       if (e == hipSuccess && verify)
         e = HIP(np::launch_verify_summary(flags, sl.r.status, n, sl.cnt, d_bad_rows + b0, s));
@@ -2965,8 +2685,8 @@ int np_restore_shards_ragged_dev(np_ctx* c, const np_code_params* p, uint8_t* d_
   if (!d_shards || !d_present) return fail(NP_ERR_INVALID_ARGUMENT);
   std::lock_guard<std::mutex> g(c->mu);  // context scratch
   (void)hipSetDevice(c->device);
-  return dev_err(launch_restore_ragged_all(c, p, d_shards, shards_size, d_present, items, batch,
-                                           reinterpret_cast<uint32_t*>(d_status), pick(c, stream)));
+  return dev_err(launch_recover_ragged_all(c, p, d_shards, shards_size, d_present, nullptr, 0, items, batch, true,
+                                           nullptr, nullptr, reinterpret_cast<uint32_t*>(d_status), pick(c, stream)));
 }
 
 int np_verify_shards_ragged_dev(np_ctx* c, const np_code_params* p, const uint8_t* d_shards, size_t shards_size,
@@ -2979,8 +2699,10 @@ int np_verify_shards_ragged_dev(np_ctx* c, const np_code_params* p, const uint8_
   if (!d_shards || !d_present || !d_bad_rows) return fail(NP_ERR_INVALID_ARGUMENT);
   std::lock_guard<std::mutex> g(c->mu);  // context scratch
   (void)hipSetDevice(c->device);
-  return dev_err(launch_verify_ragged_all(c, p, d_shards, shards_size, d_present, items, batch, d_bad_rows,
-                                          d_mismatch, reinterpret_cast<uint32_t*>(d_status), pick(c, stream)));
+  // (a verify writes no shard row)
+  return dev_err(launch_recover_ragged_all(c, p, const_cast<uint8_t*>(d_shards), shards_size, d_present, nullptr, 0,
+                                           items, batch, false, d_bad_rows, d_mismatch,
+                                           reinterpret_cast<uint32_t*>(d_status), pick(c, stream)));
 }
 
 // (Validates the items before the context, as the two calls above; the output

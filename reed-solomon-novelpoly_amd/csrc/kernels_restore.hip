@@ -21,10 +21,10 @@ namespace {
 
 constexpr uint32_t kPlanThreads = 256;
 
-// What a plan marks: the absent rows in [lo, hi) (restore), the present ones
-// (verify), or both -- the absent rows below hi and the present ones in
-// [lo, hi) -- with a second array of row words that tells the two apart (recover).
-enum PlanKind { kPlanAbsent, kPlanPresent, kPlanRecover };
+// What a plan marks (PlanKind, launchers.hpp): the absent rows in [lo, hi)
+// (restore), the present ones (verify), or both -- the absent rows below hi and
+// the present ones in [lo, hi) -- with a second array of row words that tells
+// the two apart (recover).
 
 // One workgroup per payload: the plan that marks the rows of a decoded payload
 // that KIND names.  A wave takes 64 consecutive rows at a time (one flag byte
@@ -146,14 +146,6 @@ __global__ __launch_bounds__(64 * kCopyWaves) void k_copy_absent_rows(const uint
 
 }  // namespace
 
-hipError_t launch_restore_plan(const uint8_t* present, const uint32_t* status, uint32_t n, uint32_t k,
-                               uint32_t wanted_n, size_t batch, uint32_t* plan, hipStream_t s) {
-  if (batch == 0) return hipSuccess;
-  if (batch > 0x7fffffffu || k < 64 || n % 64 != 0 || n / k > 1024) return hipErrorInvalidValue;
-  k_restore_plan<<<static_cast<uint32_t>(batch), kPlanThreads, 0, s>>>(present, status, n, k, wanted_n, batch, plan);
-  return hipGetLastError();
-}
-
 hipError_t launch_copy_absent_rows(const uint8_t* src, size_t sstride, uint8_t* dst, size_t dstride,
                                    size_t row_bytes, const uint8_t* present, const uint32_t* status, uint32_t n,
                                    uint32_t rows, size_t count, hipStream_t s) {
@@ -169,7 +161,7 @@ hipError_t launch_copy_absent_rows(const uint8_t* src, size_t sstride, uint8_t* 
 }
 
 // ------------------------------------------------------------- verify ----
-// np_verify_shards_batch_dev (engine.cpp launch_verify): the same flow with
+// np_verify_shards_batch_dev (engine.cpp launch_recover): the same flow with
 // "present" in place of "absent" and a compare in place of the store.
 //
 //  * k_verify_plan -- the plan of kernels_fast.hip k_encode_verify: bit v set
@@ -289,14 +281,6 @@ __global__ __launch_bounds__(kSummaryThreads) void k_verify_summary(const uint8_
 
 }  // namespace
 
-hipError_t launch_verify_plan(const uint8_t* present, const uint32_t* status, uint32_t n, uint32_t k,
-                              uint32_t wanted_n, size_t batch, uint32_t* plan, hipStream_t s) {
-  if (batch == 0) return hipSuccess;
-  if (batch > 0x7fffffffu || k < 64 || n % 64 != 0 || n / k > 1024) return hipErrorInvalidValue;
-  k_verify_plan<<<static_cast<uint32_t>(batch), kPlanThreads, 0, s>>>(present, status, n, k, wanted_n, batch, plan);
-  return hipGetLastError();
-}
-
 hipError_t launch_compare_present_rows(const uint8_t* enc, size_t estride, const uint8_t* recv, size_t rstride,
                                        size_t row_bytes, const uint8_t* present, const uint32_t* status, uint32_t n,
                                        uint32_t k, uint32_t rows, size_t count, uint8_t* flags, hipStream_t s) {
@@ -335,11 +319,13 @@ __global__ __launch_bounds__(kPlanThreads) void k_recover_plan(const uint8_t* __
 
 }  // namespace
 
-hipError_t launch_recover_plan(const uint8_t* present, const uint32_t* status, uint32_t n, uint32_t k,
-                               uint32_t wanted_n, size_t batch, uint32_t* plan, hipStream_t s) {
+// The plan of `kind` for each of `batch` payloads, by its kernel above.
+hipError_t launch_masked_plan(PlanKind kind, const uint8_t* present, const uint32_t* status, uint32_t n, uint32_t k,
+                              uint32_t wanted_n, size_t batch, uint32_t* plan, hipStream_t s) {
   if (batch == 0) return hipSuccess;
   if (batch > 0x7fffffffu || k < 64 || n % 64 != 0 || n / k > 1024) return hipErrorInvalidValue;
-  k_recover_plan<<<static_cast<uint32_t>(batch), kPlanThreads, 0, s>>>(present, status, n, k, wanted_n, batch, plan);
+  const auto kernel = kind == kPlanRecover ? k_recover_plan : kind == kPlanAbsent ? k_restore_plan : k_verify_plan;
+  kernel<<<static_cast<uint32_t>(batch), kPlanThreads, 0, s>>>(present, status, n, k, wanted_n, batch, plan);
   return hipGetLastError();
 }
 

@@ -191,8 +191,11 @@ hipError_t configure_huge_kernels();
 // below wanted_n, and the payload's status (ReconstructArgs::status layout) OK.
 constexpr size_t restore_seg_words(uint32_t n, uint32_t k) { return (n / k + 31) / 32; }
 constexpr size_t restore_plan_words(uint32_t n, uint32_t k) { return restore_seg_words(n, k) + n / 32; }
-hipError_t launch_restore_plan(const uint8_t* present, const uint32_t* status, uint32_t n, uint32_t k,
-                               uint32_t wanted_n, size_t batch, uint32_t* plan, hipStream_t s);
+// What a plan marks: the absent rows below wanted_n (restore), the present ones
+// in [k, wanted_n) (verify, below), or both, told apart (recover, further below).
+enum PlanKind { kPlanAbsent, kPlanPresent, kPlanRecover };
+hipError_t launch_masked_plan(PlanKind kind, const uint8_t* present, const uint32_t* status, uint32_t n, uint32_t k,
+                              uint32_t wanted_n, size_t batch, uint32_t* plan, hipStream_t s);
 // k in {64, 128, 256}, every n of the fast encode: the single-tile encode that
 // stores only the plan's rows and skips the transforms of segments without one.
 bool masked_encode_supported(uint32_t n, uint32_t k);
@@ -211,8 +214,6 @@ hipError_t bounds_take_restore(uint32_t out[8]);
 // flags: n bytes per payload, zeroed by the caller before the compare; a
 // kernel sets flags[b * n + v] = 1 when row v of payload b differs from the
 // re-encoding and writes nothing else.
-hipError_t launch_verify_plan(const uint8_t* present, const uint32_t* status, uint32_t n, uint32_t k,
-                              uint32_t wanted_n, size_t batch, uint32_t* plan, hipStream_t s);
 // Where masked_encode_supported: the masked encode's flow with a compare of the
 // plan's rows against a.shards (read only) in place of the store.
 hipError_t launch_encode_verify(const DevTables& T, const EncodeArgs& a, const uint32_t* plan, uint8_t* flags,
@@ -235,8 +236,6 @@ hipError_t launch_verify_summary(const uint8_t* flags, const uint32_t* status, u
 // then n / 32 words with bit v set when row v of the union is stored (absent);
 // the other rows of the union are compared.
 constexpr size_t recover_plan_words(uint32_t n, uint32_t k) { return restore_plan_words(n, k) + n / 32; }
-hipError_t launch_recover_plan(const uint8_t* present, const uint32_t* status, uint32_t n, uint32_t k,
-                               uint32_t wanted_n, size_t batch, uint32_t* plan, hipStream_t s);
 // Where masked_encode_supported: the masked encode's flow; a.shards holds the
 // received rows, of which the plan's absent ones are written and its present
 // ones compared (flags as launch_encode_verify).
@@ -285,7 +284,7 @@ bool ragged_masked_supported(uint32_t n, uint32_t k);
 // k_encode_masked's / k_encode_verify's flow per block-table entry.  The
 // records name the decoded payload of an item ({address, (shard_len / 2) * 2k})
 // and its shard rows; plan: restore_plan_words(n, k) words per item
-// (launch_restore_plan / launch_verify_plan); flags: n bytes per item.
+// (launch_masked_plan, kPlanAbsent / kPlanPresent); flags: n bytes per item.
 // r.data_base / r.data_size: the payload scratch; r.present and r.status: what
 // the plan was made from (checked builds arm their extents).
 hipError_t launch_encode_masked_ragged(const DevTables& T, const RaggedArgs& r, const uint32_t* plan, hipStream_t s);
@@ -296,7 +295,7 @@ hipError_t launch_encode_verify_ragged(const DevTables& T, const RaggedArgs& r, 
 // k_encode_recover's flow per block-table entry, on the records of the masked
 // launches above (r.data_base / r.data_size: the payload scratch, or the
 // caller's output buffer that took the decode).  plan: recover_plan_words(n, k)
-// words per item (launch_recover_plan); flags: n bytes per item.
+// words per item (launch_masked_plan, kPlanRecover); flags: n bytes per item.
 hipError_t launch_encode_recover_ragged(const DevTables& T, const RaggedArgs& r, const uint32_t* plan, uint8_t* flags,
                                         hipStream_t s);
 }  // namespace np

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import novelpoly_amd as npa
+from _rs_front import CTX, K, LEN, N, NEED, check_front, outcome, params, poison, received
 from novelpoly_amd import synth
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
@@ -153,3 +154,34 @@ def test_batch_split_contiguous_ranges():
             sizes = [c for _, c in rng]
             assert max(sizes) - min(sizes) <= 1 and sizes == sorted(sizes, reverse=True)
     assert npa.batch_split(10, 2, 5) == (10, 0)  # out-of-range device: empty
+
+
+def _rs_reconstruct(p, ptrs, lens, n_received, out=CTX, cap=NEED, out_len="len"):
+    if out_len == "len":
+        out_len = C.byref(C.c_size_t())
+    return npa.lib().np_rs_reconstruct(CTX, C.byref(p) if p is not None else None, ptrs, lens, n_received, out, cap,
+                                       out_len)
+
+
+def test_rs_reconstruct_validates_the_received_set():
+    """Against a zero-filled stand-in for the context: every case returns before it is touched."""
+    check_front(_rs_reconstruct)
+
+
+def test_rs_reconstruct_checks_its_output_after_the_code():
+    """NULL `out` or `out_len`, or a `cap` below the padded payload: detail (that
+    length), after the received set and the code."""
+    ptrs, lens = received()
+    for kw in (dict(out=None), dict(out_len=None), dict(cap=NEED - 1), dict(out=None, cap=0, out_len=None)):
+        poison()
+        assert outcome(_rs_reconstruct(params(), ptrs, lens, N, **kw)) == (100, (NEED, 0, 0)), kw
+        poison()
+        assert outcome(_rs_reconstruct(params(64, 16, 65), ptrs, lens, N, **kw)) == (100, (64, 16, 65)), kw
+        poison()
+        assert outcome(_rs_reconstruct(params(), *received(K - 1), N, **kw)) \
+            == (npa.NeedMoreShards.code, (K - 1, K, N)), kw
+    # the padded length: LEN - 1 received bytes still decode to NEED
+    for i in range(K):
+        lens[i] = LEN - 1
+    poison()
+    assert outcome(_rs_reconstruct(params(), ptrs, lens, N, cap=NEED - 1)) == (100, (NEED, 0, 0))

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 import novelpoly_amd as npa
+from _rs_front import CTX, N, check_front, outcome, params, poison, received
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("np_verify_shards_batch_dev", "np_rs_verify_shards")
@@ -120,6 +121,57 @@ def test_validation_runs_before_any_device_call():
     assert L.np_rs_verify_shards(None, C.byref(p), ptrs, lens, 0, C.byref(bad), None) == 100
     with pytest.raises(npa.InvalidArgument):
         npa._raise(100)
+
+
+def _dev(p, shards, present, bad, shard_len=600, stride=1024 * 600, mismatch=None, status=None):
+    poison()
+    return outcome(npa.lib().np_verify_shards_batch_dev(CTX, C.byref(p) if p is not None else None, shards, shard_len,
+                                                        stride, present, 1, bad, mismatch, status, None))
+
+
+def test_device_call_validation_order():
+    """Every case returns before the context (a zero-filled stand-in) is touched;
+    where two faults are present the earlier check's is reported."""
+    buf = CTX
+    p = npa._Params(1024, 256, 1024)
+    inv = (100, (0, 0, 0))
+    # the code: before a bad shard length and before NULL buffers
+    assert _dev(None, buf, buf, buf) == inv
+    assert _dev(npa._Params(1000, 300, 1000), None, None, None, shard_len=0) \
+        == (npa.ParamterMustBePowerOf2.code, (1000, 300, 0))
+    assert _dev(npa._Params(1024, 768, 1024), None, None, None, shard_len=0) == (100, (1024, 768, 1024))  # 2k > n
+    assert _dev(npa._Params(1024, 256, 1025), buf, buf, buf, shard_len=601) == (100, (1024, 256, 1025))
+    # a zero or odd shard length: before NULL buffers (the counts among them) and a short stride
+    assert _dev(p, None, None, None, shard_len=0) == (npa.EmptyShard.code, (0, 0, 0))
+    assert _dev(p, buf, buf, None, shard_len=601, stride=0) == (npa.EmptyShard.code, (0, 0, 0))
+    # NULL buffers, a stride below n rows
+    assert _dev(p, None, buf, buf) == inv
+    assert _dev(p, buf, None, buf) == inv
+    assert _dev(p, buf, buf, None) == inv
+    assert _dev(p, buf, buf, None, mismatch=buf, status=buf) == inv
+    assert _dev(p, buf, buf, buf, stride=1024 * 600 - 1) == inv
+
+
+def _host(p, ptrs, lens, n_received, bad="count", mismatch=None):
+    if bad == "count":
+        bad = C.byref(C.c_size_t())
+    return npa.lib().np_rs_verify_shards(CTX, C.byref(p) if p is not None else None, ptrs, lens, n_received, bad,
+                                         mismatch)
+
+
+def test_host_call_validates_the_received_set():
+    check_front(_host)
+    check_front(lambda *a: _host(*a, mismatch=CTX))
+
+
+def test_host_call_rejects_null_bad_rows_first():
+    """Before the code and before the count of the received shards."""
+    ptrs, lens = received()
+    for p, rx in ((params(), (ptrs, lens, N)), (params(12, 3, 12), (ptrs, lens, N)), (params(), (None, None, 0)),
+                  (params(64, 16, 65), (ptrs, lens, N))):
+        for mismatch in (None, CTX):
+            poison()
+            assert outcome(_host(p, *rx, bad=None, mismatch=mismatch)) == (100, (0, 0, 0))
 
 
 def test_header_and_rust_binding_declare_them():
