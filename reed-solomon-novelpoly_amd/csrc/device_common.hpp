@@ -189,6 +189,18 @@ __device__ __forceinline__ BoundsSet bounds_for(const ReconstructArgs& a, const 
   return bounds_of(a, T, 0);  // (records of other layouts: unchecked)
 }
 
+// Raises the dynamic-LDS limit of kernel instances above the 64 KiB default;
+// err: the first failure.
+struct LdsSetup {
+  hipError_t err = hipSuccess;
+  template <typename KERN>
+  void operator()(KERN* f, size_t bytes) {
+    const hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void*>(f),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
+    if (r != hipSuccess && err == hipSuccess) err = r;
+  }
+};
+
 // Host side of a translation unit: its first violation record since the last
 // call (out[0] = count), then cleared.  hipErrorNotSupported in the product.
 inline hipError_t bounds_take_tu(uint32_t out[kBoundsRecordWords]) {

@@ -655,18 +655,36 @@ const char* np_status_message(int st) {
   }
 }
 
+// The kernel translation units: the dynamic-LDS set-up a unit needs once per
+// device (np_ctx_create; nullptr: none) and its bounds record of the checked
+// build (np_debug_bounds_check).  kernels_systematic.hip has neither.
+struct KernelUnit {
+  hipError_t (*configure)();
+  hipError_t (*bounds_take)(uint32_t*);
+};
+static const KernelUnit kKernelUnits[] = {
+    {np::configure_generic_kernels, np::bounds_take_generic},
+    {np::configure_fast_encode_kernels, np::bounds_take_fast_encode},
+    {np::configure_fast_planned_kernels, np::bounds_take_fast_planned},
+    {np::configure_fast_decode_kernels, np::bounds_take_fast_decode},
+    {nullptr, np::bounds_take_fast_records},
+    {np::configure_res_kernels, np::bounds_take_res},
+    {nullptr, np::bounds_take_small},
+    {np::configure_big_kernels, np::bounds_take_big},
+    {np::configure_huge_kernels, np::bounds_take_huge},
+    {nullptr, np::bounds_take_restore},
+};
+
 int np_debug_bounds_check(np_ctx* c, uint32_t out[8]) {
   if (!c || !out) return fail(NP_ERR_INVALID_ARGUMENT);
   (void)hipSetDevice(c->device);
   for (int i = 0; i < 8; ++i) out[i] = 0;
   hipError_t e = HIP(hipDeviceSynchronize());
   if (e != hipSuccess) return dev_err(e);
-  hipError_t (*const take[])(uint32_t*) = {np::bounds_take_generic, np::bounds_take_fast, np::bounds_take_res,
-                                            np::bounds_take_small, np::bounds_take_big, np::bounds_take_huge,
-                                            np::bounds_take_restore};
-  for (auto f : take) {
+  for (const KernelUnit& u : kKernelUnits) {
+    if (!u.bounds_take) continue;
     uint32_t r[8];
-    e = f(r);
+    e = u.bounds_take(r);
     if (e == hipErrorNotSupported) return fail(NP_ERR_INVALID_ARGUMENT);  // the product build: no checks
     if (e != hipSuccess) return dev_err(HIP(e));
     if (r[0] && !out[0])
@@ -778,11 +796,8 @@ int np_ctx_create(int device, np_ctx** out) {
   if (e == hipSuccess) {
     std::lock_guard<std::mutex> g(g_cfg_mu);
     if (std::find(g_configured_devices.begin(), g_configured_devices.end(), device) == g_configured_devices.end()) {
-      e = np::configure_generic_kernels();
-      if (e == hipSuccess) e = np::configure_fast_kernels();
-      if (e == hipSuccess) e = np::configure_big_kernels();
-      if (e == hipSuccess) e = np::configure_res_kernels();
-      if (e == hipSuccess) e = np::configure_huge_kernels();
+      for (const KernelUnit& u : kKernelUnits)
+        if (e == hipSuccess && u.configure) e = u.configure();
       if (e == hipSuccess) g_configured_devices.push_back(device);
     }
   }
@@ -1078,7 +1093,7 @@ hipError_t after(hipError_t e, hipStream_t s, int line, const char* step) {
 
 // Rows of each payload the reconstruct kernels read: on the fast, resident,
 // huge and big paths only the k systematic rows when all of them are present
-// (the output is those rows: kernels_fast.hip k_prefix_locator, kernels_huge.hip
+// (the output is those rows: kernels_fast_records.hip k_prefix_locator, kernels_huge.hip
 // k_huge_records, kernels_big.hip kBigCopy), otherwise -- and on the generic
 // path -- all n rows: the reference decodes from every present row
 // (inc_reconstruct.rs:61-85).  The path is the one launch_reconstruct takes
@@ -2137,7 +2152,7 @@ int np_reconstruct_from_systematic_batch_dev(np_ctx* c, const np_code_params* p,
 // Direct shapes (k in {64, 128, 256}): the host plans one workgroup per item
 // and 256-column tile (ragged_plan), uploads the item records and the block
 // table through pinned staging into context scratch, and launches the ragged
-// kernels of kernels_fast.hip.  Every other shape: runs of equal items at a
+// kernels of kernels_fast_*.hip.  Every other shape: runs of equal items at a
 // constant spacing through the uniform launch_encode / launch_reconstruct.
 // np_restore_shards_ragged_dev / np_verify_shards_ragged_dev run
 // the ragged reconstruct into the restore scratch and the ragged masked /
@@ -2147,7 +2162,7 @@ int np_reconstruct_from_systematic_batch_dev(np_ctx* c, const np_code_params* p,
 // recover encode.
 namespace {
 
-constexpr size_t kRaggedTile = 256;  // columns per workgroup (kernels_fast.hip kTile)
+constexpr size_t kRaggedTile = 256;  // columns per workgroup (fast_common.hpp kTile)
 
 bool past(uint64_t off, uint64_t len, uint64_t size) { return off > size || len > size - off; }
 

@@ -1,18 +1,24 @@
-// Shared building blocks of the specialised gfx950 kernels (kernels_fast.hip,
+// Shared building blocks of the specialised gfx950 kernels (kernels_fast_*.hip,
 // kernels_big.hip): tile geometry and LDS swizzle, the v_perm GF(2^16)
 // multiply, multiplier-table fetch and staging, the column-quad and high
 // register layouts with their transform levels, and the folded erasure
-// locator.  See kernels_fast.hip for the design.
+// locator.  See kernels_fast_encode.hip for the design.
 #pragma once
 #include <type_traits>
 
 #include "device_common.hpp"
+#include "launch_common.hpp"
 #include "launchers.hpp"
 
 namespace np {
 namespace {
 
 constexpr int kTile = 256;  // columns per workgroup
+
+// The columns of an encode launch, and what a launcher returns for a grid it
+// does not launch (launch_common.hpp tile_grid).
+inline size_t encode_chunks(const EncodeArgs& a) { return (a.payload_len + 2 * a.k - 1) / (2 * a.k); }  // per payload
+inline hipError_t grid_status(const TileGrid& g) { return g.state == kGridInvalid ? hipErrorInvalidValue : hipSuccess; }
 
 // Experiment builds only (tools/exp_variants.sh; the product is built with 0):
 // bit 0 skips the transform levels, bit 1 the shard stores, bit 2 the payload
@@ -110,7 +116,7 @@ __host__ __device__ constexpr uint32_t swz(uint32_t cs) {
 // for disjoint bit sets.
 // EVEN: the swizzle with bit 0 cleared, so blocks 2i and 2i + 1 of a column
 // stay a contiguous, 16-byte aligned pair (the multi-tile encode's payload
-// tile with 16-byte LDS-DMA pieces, kernels_fast.hip NP_ENC_DMA_X4: its cq
+// tile with 16-byte LDS-DMA pieces, kernels_fast_encode.hip NP_ENC_DMA_X4: its cq
 // reads then conflict 2-way).
 template <int K, bool EVEN = false>
 __host__ __device__ constexpr uint32_t col_base_c(uint32_t c) {
@@ -591,9 +597,6 @@ __device__ __forceinline__ void store_rows(uint8_t* out, size_t shard_len, uint3
 // the 20 table dwords of group f+1 are requested before group f executes.  The
 // scheduling barriers stop the compiler from hoisting the s_loads of a whole
 // pass (20 SGPRs each) ahead of their use, which spills SGPRs into VGPRs.
-template <int F>
-using Int = std::integral_constant<int, F>;
-
 template <int F, int NG, typename CF, typename GF>
 __device__ __forceinline__ void pipe_step(const DevTables& T, CF& cval, GF& group, uint32_t (&cur)[20],
                                           uint32_t (&nxt)[20]) {
@@ -849,9 +852,9 @@ __device__ __forceinline__ void qbfly_fwd_conv(uint32_t& xl, uint32_t& xh, uint3
 // groups, 0 in the last), so the waves of a SIMD that are behind issue first
 // and the four reach the pass's closing barrier together, instead of in age
 // order (a SIMD favours its older waves).  The callers choose per kernel
-// (kernels_fast.hip kEncPrio / kRecPrio*).
+// (fast_family.hpp kEncPrio / kRecPrio*).
 // PRIO 1: 3, 2, 1, 0 over the pass's quarters; 2: 3 throughout; 3: 1, 1, 0, 0;
-// 4: 3, 3, 2, 2 (passes inside a longer barrier-free span, kernels_fast.hip
+// 4: 3, 3, 2, 2 (passes inside a longer barrier-free span, fast_family.hpp
 // kRecPrioSpan / kEncPrio).
 template <int F, int NG, int PRIO>
 __device__ __forceinline__ void progress_prio() {

@@ -25,7 +25,7 @@ struct HostTables {
   // [0, n) equals two n-point Walsh transforms around F_n, mod 65535).
   std::vector<uint16_t> lw_fold;
   // Per additive multiplier c (65536 of them): byte tables for the v_perm
-  // multiplier (kernels_fast.hip, "GF multiply"); 20 dwords each.
+  // multiplier (fast_common.hpp, "GF multiply"); 20 dwords each.
   std::vector<uint32_t> perm_pools;
 
   // Tower coordinates of the fast kernels.  GF(2^16) = GF(2^8) + gamma GF(2^8)

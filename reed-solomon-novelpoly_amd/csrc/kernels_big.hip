@@ -371,7 +371,7 @@ __global__ __launch_bounds__(kTB) __attribute__((amdgpu_waves_per_eu(4))) void k
 }
 
 // ------------------------------------------------------------- reconstruct ----
-// n = NQ * KB.  As in k_reconstruct_fast (kernels_fast.hip), the first KB
+// n = NQ * KB.  As in k_reconstruct_fast (kernels_fast_decode.hip), the first KB
 // outputs are out = FFT(KB, 0)(d) with
 //   d = D_KB(x0) ^ sum_q kappa_q x_q,  x_q = IFFT(KB, KB q)(premultiplied segment q)
 // (kappa: NQ = 2 (1, 1); NQ = 4 (0, 1, 3, 2); NQ = 8 rec8_kappa; Cantor
@@ -389,7 +389,7 @@ __host__ __device__ constexpr uint32_t big_kappa(int q) {
     constexpr uint32_t k[4] = {0, 1, 3, 2};
     return k[q];
   } else {
-    constexpr uint32_t k[8] = {1, 1, 3, 2, 12, 15, 10, 8};  // kernels_fast.hip rec8_kappa
+    constexpr uint32_t k[8] = {1, 1, 3, 2, 12, 15, 10, 8};  // kernels_fast_decode.hip rec8_kappa
     return k[q];
   }
 }
@@ -910,30 +910,32 @@ static_assert(enc_big_lds() <= 160u * 1024u, "encode LDS");
 static_assert(16384 / 256 <= 64, "sub-segment occupancy is one u64");
 static_assert(rec_big_lds(8192) <= 160u * 1024u, "largest reconstruct instance (k = 1024 / 2048, n = 8192) LDS");
 
+using BigKs = Ints<512, 1024, 2048>;
+
 // Calls f(reconstruct kernel, record kernel) for the instances of (n, k);
 // false if none.
 template <typename F>
 bool with_rec_big(uint32_t n, uint32_t k, F&& f) {
-  if (k == 512) {
-    if (n == 1024) return f(&k_reconstruct_big<512, 2>, &k_big_records<512, 1024>), true;
-    if (n == 2048) return f(&k_reconstruct_big<512, 4>, &k_big_records<512, 2048>), true;
-    if (n == 4096) return f(&k_reconstruct_big<512, 8>, &k_big_records<512, 4096>), true;
-  } else if (k == 1024) {
-    if (n == 2048) return f(&k_reconstruct_big<1024, 2>, &k_big_records<1024, 2048>), true;
-    if (n == 4096) return f(&k_reconstruct_big<1024, 4>, &k_big_records<1024, 4096>), true;
-    if (n == 8192) return f(&k_reconstruct_big<1024, 8>, &k_big_records<1024, 8192>), true;
-  } else if (k == 2048) {
-    if (n == 4096) return f(&k_reconstruct_big<2048, 2>, &k_big_records<2048, 4096>), true;
-    if (n == 8192) return f(&k_reconstruct_big<2048, 4>, &k_big_records<2048, 8192>), true;
-    if (n == 16384) return f(&k_reconstruct_big<2048, 8>, &k_big_records<2048, 16384>), true;
-  }
-  return false;
+  return with_k(BigKs{}, k, false, [&](auto kc) {
+    constexpr int K = kc.value;
+    return with_nq(n, k, false, [&](auto qc) {
+      constexpr int NQ = qc.value;
+      f(&k_reconstruct_big<K, NQ>, &k_big_records<K, NQ * K>);
+      return true;
+    });
+  });
+}
+
+// The encode instance of k (k = 2048's for a k outside the list).
+const void* enc_big_kernel(uint32_t k) {
+  return with_k(BigKs{}, k, reinterpret_cast<const void*>(&k_encode_big<2048>),
+                [](auto kc) { return reinterpret_cast<const void*>(&k_encode_big<kc.value>); });
 }
 
 }  // namespace
 
 bool big_encode_supported(uint32_t n, uint32_t k) {
-  return (k == 512 || k == 1024 || k == 2048) && n >= 2 * k && n <= 65536;
+  return k_in(BigKs{}, k) && n >= 2 * k && n <= 65536;
 }
 bool big_reconstruct_supported(uint32_t n, uint32_t k) {
   return with_rec_big(n, k, [](auto, auto) {});
@@ -982,37 +984,28 @@ size_t big_resident_slots(int device, uint32_t n, uint32_t k, bool reconstruct) 
     with_rec_big(n, k, [&](auto kf, auto) { kern = reinterpret_cast<const void*>(kf); });
     return kern ? resident_slots_of(device, kern, rec_big_lds(n)) : 8;
   }
-  kern = k == 512 ? reinterpret_cast<const void*>(&k_encode_big<512>)
-         : k == 1024 ? reinterpret_cast<const void*>(&k_encode_big<1024>)
-                     : reinterpret_cast<const void*>(&k_encode_big<2048>);
-  return resident_slots_of(device, kern, enc_big_lds());
+  return resident_slots_of(device, enc_big_kernel(k), enc_big_lds());
 }
 
 hipError_t launch_encode_big(const DevTables& T, const EncodeArgs& a, uint8_t* scratch, size_t scratch_bytes,
                              hipStream_t s) {
   if (!big_encode_supported(a.n, a.k)) return hipErrorInvalidValue;
-  const size_t nchunks = (a.payload_len + 2 * a.k - 1) / (2 * a.k);
+  const size_t nchunks = encode_chunks(a);
   if (nchunks == 0 || a.batch == 0) return hipSuccess;
   const uint32_t tiles = static_cast<uint32_t>((nchunks + kTile - 1) / kTile);
   const size_t total = a.batch * tiles;
   // multiple of 8 keeps tile0 % 8 == 0 (tile_of)
   const size_t per_tile = big_encode_scratch_per_tile(a.k);
-  const void* kern = a.k == 512 ? reinterpret_cast<const void*>(&k_encode_big<512>)
-                     : a.k == 1024 ? reinterpret_cast<const void*>(&k_encode_big<1024>)
-                                   : reinterpret_cast<const void*>(&k_encode_big<2048>);
-  const size_t per_launch = std::min(resident_slots_of(current_device(), kern, enc_big_lds()), scratch_bytes / per_tile / 8 * 8);
+  const size_t per_launch =
+      std::min(resident_slots_of(current_device(), enc_big_kernel(a.k), enc_big_lds()), scratch_bytes / per_tile / 8 * 8);
   if (per_launch == 0 || total > 0xffffffffu) return hipErrorInvalidValue;
   for (size_t t0 = 0; t0 < total; t0 += per_launch) {
     const uint32_t blocks = static_cast<uint32_t>(std::min(per_launch, total - t0));
-    if (a.k == 512)
-      k_encode_big<512><<<blocks, kTB, enc_big_lds(), s>>>(T, a, static_cast<uint32_t>(nchunks), tiles,
-                                                            static_cast<uint32_t>(t0), scratch);
-    else if (a.k == 1024)
-      k_encode_big<1024><<<blocks, kTB, enc_big_lds(), s>>>(T, a, static_cast<uint32_t>(nchunks), tiles,
-                                                             static_cast<uint32_t>(t0), scratch);
-    else
-      k_encode_big<2048><<<blocks, kTB, enc_big_lds(), s>>>(T, a, static_cast<uint32_t>(nchunks), tiles,
-                                                             static_cast<uint32_t>(t0), scratch);
+    with_k(BigKs{}, a.k, false, [&](auto kc) {
+      k_encode_big<kc.value><<<blocks, kTB, enc_big_lds(), s>>>(T, a, static_cast<uint32_t>(nchunks), tiles,
+                                                                 static_cast<uint32_t>(t0), scratch);
+      return true;
+    });
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
@@ -1056,18 +1049,12 @@ hipError_t launch_reconstruct_big(const DevTables& T, const ReconstructArgs& a, 
 }
 
 hipError_t configure_big_kernels() {
-  hipError_t e = hipSuccess;
-  auto set = [&](const void* f, size_t bytes) {
-    hipError_t r = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
-    if (r != hipSuccess && e == hipSuccess) e = r;
-  };
-  set(reinterpret_cast<const void*>(&k_encode_big<512>), enc_big_lds());
-  set(reinterpret_cast<const void*>(&k_encode_big<1024>), enc_big_lds());
-  set(reinterpret_cast<const void*>(&k_encode_big<2048>), enc_big_lds());
-  for (uint32_t k : {512u, 1024u, 2048u})
-    for (uint32_t nq : {2u, 4u, 8u})
-      with_rec_big(nq * k, k, [&](auto kern, auto) { set(reinterpret_cast<const void*>(kern), rec_big_lds(nq * k)); });
-  return e;
+  LdsSetup lds;
+  for (uint32_t k : {512u, 1024u, 2048u}) {
+    lds(enc_big_kernel(k), enc_big_lds());
+    for (uint32_t nq : {2u, 4u, 8u}) with_rec_big(nq * k, k, [&](auto kern, auto) { lds(kern, rec_big_lds(nq * k)); });
+  }
+  return lds.err;
 }
 
 hipError_t bounds_take_big(uint32_t out[8]) { return bounds_take_tu(out); }

@@ -3,7 +3,7 @@
 // tile of codeword columns held in LDS; its 256 threads sweep the butterflies
 // of each transform level.  The multiply is the crate's LOG/EXP gather
 // (inc_log_mul.rs:42-49) from L2-resident tables, so this path is the
-// correctness fallback, not the fast path (kernels_fast.hip).
+// correctness fallback, not the fast path (kernels_fast_*.hip).
 #include "device_common.hpp"
 #include "launchers.hpp"
 
@@ -429,22 +429,18 @@ inline uint32_t grid_x(size_t total, uint32_t per) { return static_cast<uint32_t
 }  // namespace
 
 hipError_t configure_generic_kernels() {
-  const int lim = 160 * 1024;
-  hipError_t e = hipSuccess;
-  auto set = [&](const void* f) {
-    hipError_t r = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-    if (r != hipSuccess && e == hipSuccess) e = r;
-  };
-  set(reinterpret_cast<const void*>(&k_encode_generic));
-  set(reinterpret_cast<const void*>(&k_reconstruct_generic));
-  set(reinterpret_cast<const void*>(&k_error_locator<true>));
-  set(reinterpret_cast<const void*>(&k_error_locator<false>));
-  set(reinterpret_cast<const void*>(&k_afft_cols<true>));
-  set(reinterpret_cast<const void*>(&k_afft_cols<false>));
-  set(reinterpret_cast<const void*>(&k_walsh));
-  set(reinterpret_cast<const void*>(&k_encode_low));
-  set(reinterpret_cast<const void*>(&k_decode_main));
-  return e;
+  const size_t lim = 160 * 1024;
+  LdsSetup lds;
+  lds(&k_encode_generic, lim);
+  lds(&k_reconstruct_generic, lim);
+  lds(&k_error_locator<true>, lim);
+  lds(&k_error_locator<false>, lim);
+  lds(&k_afft_cols<true>, lim);
+  lds(&k_afft_cols<false>, lim);
+  lds(&k_walsh, lim);
+  lds(&k_encode_low, lim);
+  lds(&k_decode_main, lim);
+  return lds.err;
 }
 
 hipError_t launch_encode_generic(const DevTables& T, const EncodeArgs& a, hipStream_t s) {

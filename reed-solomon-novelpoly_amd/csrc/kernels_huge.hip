@@ -28,7 +28,7 @@
 //   k_huge_enc_fwd  per (s, m): FFT(1024, sk + 1024 m) of slot s M + m -> shard
 //                   rows sk + 1024 m ...
 // Reconstruct (inc_reconstruct.rs:1-113, mod.rs:162-239; the fold of
-// kernels_fast.hip / DESIGN.md §4.3 with n = NQ k):
+// kernels_fast_decode.hip / DESIGN.md §4.3 with n = NQ k):
 //   k_huge_records  status and mode per payload (skip / copy / decode), and
 //                   which 1024-row blocks hold a present row;
 //   locators        the generic 65536-point Walsh kernel (or the caller's);
@@ -429,7 +429,7 @@ __device__ __forceinline__ void huge_rec_inv_body(
   }
 }
 
-// Fold coefficients kappa_q (Cantor coordinates, kernels_fast.hip):
+// Fold coefficients kappa_q (Cantor coordinates, kernels_fast_decode.hip):
 // NQ = 2: (1, 1); NQ = 4: (0, 1, 1 + beta, beta), beta = Cantor(2); NQ = 8:
 // rec8_kappa.
 template <int NQ>
@@ -634,25 +634,8 @@ NP_HUGE_PHASE(huge_rec_fwd, (DevTables T, ReconstructArgs a, HugeArgs h, uint32_
 #undef NP_HUGE_PHASE
 
 // ------------------------------------------------------------ dispatch ----
-template <typename F>
-hipError_t with_m(uint32_t M, F&& f) {
-  switch (M) {
-    case 2: return f(Int<2>{});
-    case 4: return f(Int<4>{});
-    case 8: return f(Int<8>{});
-    case 16: return f(Int<16>{});
-    default: return hipErrorInvalidValue;
-  }
-}
-template <typename F>
-hipError_t with_nq(uint32_t NQ, F&& f) {
-  switch (NQ) {
-    case 2: return f(Int<2>{});
-    case 4: return f(Int<4>{});
-    case 8: return f(Int<8>{});
-    default: return hipErrorInvalidValue;
-  }
-}
+// M = k / 1024 of the top-level kernels.
+using HugeMs = Ints<2, 4, 8, 16>;
 
 // NP_HUGE_PAIR=0 (experiment knob, read once): one payload per tile always.
 bool huge_pair_enabled() {
@@ -678,7 +661,7 @@ HugeArgs huge_args(uint8_t* scr, uint32_t n, uint32_t k, size_t tiles, uint32_t 
 
 bool huge_encode_supported(uint32_t n, uint32_t k) { return k >= 2048 && k <= 16384 && n >= 2 * k && n <= 65536; }
 bool huge_reconstruct_supported(uint32_t n, uint32_t k) {
-  return k >= 2048 && k <= 16384 && (n == 2 * k || n == 4 * k || n == 8 * k) && n <= 65536;
+  return k >= 2048 && k <= 16384 && nq_supported(n, k) && n <= 65536;
 }
 size_t huge_encode_scratch_per_payload(size_t shard_len, uint32_t n, uint32_t k) {
   (void)k;
@@ -722,7 +705,7 @@ hipError_t launch_encode_huge(const DevTables& T, const EncodeArgs& a, uint8_t* 
   hipError_t e = hipGetLastError();
   const size_t units = per * 16 * kSK;
   if (e == hipSuccess)
-    e = with_m(h.M, [&](auto mc) {
+    e = with_k(HugeMs{}, h.M, hipErrorInvalidValue, [&](auto mc) {
       k_huge_enc_top<decltype(mc)::value><<<static_cast<uint32_t>(units / 256), 256, 0, s>>>(T, h, h.NQ, a.wanted_n, units);
       return hipGetLastError();
     });
@@ -772,8 +755,8 @@ hipError_t launch_reconstruct_huge(const DevTables& T, const ReconstructArgs& a,
   }
   const size_t units = per * 16 * kSK;
   if (e == hipSuccess)
-    e = with_m(h.M, [&](auto mc) {
-      return with_nq(h.NQ, [&](auto qc) {
+    e = with_k(HugeMs{}, h.M, hipErrorInvalidValue, [&](auto mc) {
+      return with_nq(a.n, a.k, hipErrorInvalidValue, [&](auto qc) {
         k_huge_rec_top<decltype(mc)::value, decltype(qc)::value>
             <<<static_cast<uint32_t>(units / 256), 256, 0, s>>>(T, h, units);
         return hipGetLastError();
@@ -788,16 +771,12 @@ hipError_t launch_reconstruct_huge(const DevTables& T, const ReconstructArgs& a,
 }
 
 hipError_t configure_huge_kernels() {
-  hipError_t e = hipSuccess;
-  auto set = [&](const void* f) {
-    const hipError_t r = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kHugeLds));
-    if (r != hipSuccess && e == hipSuccess) e = r;
-  };
-  set(reinterpret_cast<const void*>(&k_huge_enc_inv));
-  set(reinterpret_cast<const void*>(&k_huge_enc_fwd));
-  set(reinterpret_cast<const void*>(&k_huge_rec_inv));
-  set(reinterpret_cast<const void*>(&k_huge_rec_fwd));
-  return e;
+  LdsSetup lds;
+  lds(&k_huge_enc_inv, kHugeLds);
+  lds(&k_huge_enc_fwd, kHugeLds);
+  lds(&k_huge_rec_inv, kHugeLds);
+  lds(&k_huge_rec_fwd, kHugeLds);
+  return lds.err;
 }
 
 hipError_t bounds_take_huge(uint32_t out[8]) { return bounds_take_tu(out); }

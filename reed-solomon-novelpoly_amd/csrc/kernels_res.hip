@@ -154,7 +154,7 @@ __device__ __forceinline__ bool res_step(const DevTables& T, const ReconstructAr
   const Res rr = res_coords<K>();  // opaque per step: lane-derived values are not hoisted across steps
   uint32_t XL[16], XH[16];
   // 8 segments: a segment without a present row gives x_q = 0 (record byte 1,
-  // kernels_fast.hip segment_occupancy; e.g. the rows past wanted_n at 2,500,
+  // kernels_fast_records.hip segment_occupancy; e.g. the rows past wanted_n at 2,500,
   // 3,000 and 5,000 validators): no loads, transform or exchanges, only the
   // next step's row tables and the fold.
   if (NQ == 8 && !((occ >> q) & 1u)) {
@@ -255,7 +255,7 @@ __device__ __forceinline__ bool res_step(const DevTables& T, const ReconstructAr
   rstamp(dbg, s0 + 6);
   }
   }
-  // fold x_q into d (kernels_fast.hip rec_segments)
+  // fold x_q into d (kernels_fast_decode.hip rec_segments)
   if constexpr (NQ == 8 && q != 0 && rec8_kappa_res(q) != 1u) {  // d ^= kappa_q x_q, kappa_q in GF(16)
     uint32_t kp[20];
     pool_of<true>(T, rec8_kappa_res(q), kp);
@@ -400,7 +400,7 @@ __device__ __forceinline__ void res_copy_tile(const ReconstructArgs& a, const ui
 // One workgroup per 64-column tile.  SERVE = 1: payloads whose record says
 // copy (nq = 1); 2: decodes from 2 segments (n = 2K, or a trusted prefix of
 // n = 4K); 4 / 8: the 4- / 8-segment decodes.  The host launches the
-// instances over the same grid (kernels_fast.hip's scheme).
+// instances over the same grid (kernels_fast_decode.hip's scheme).
 template <int K, int SERVE>
 __global__ __launch_bounds__(K) __attribute__((amdgpu_waves_per_eu(4))) void k_reconstruct_res(
     DevTables T, ReconstructArgs a, uint32_t nsyms, uint32_t tiles) {
@@ -445,7 +445,7 @@ bool res_enabled() {
 }
 
 // k = 512 and 1024 with n / k in {2, 4, 8} (n <= 8K: res_gen <= 5).
-bool res_encode_supported(uint32_t n, uint32_t k) { return (k == 512 || k == 1024) && (n == 2 * k || n == 4 * k || n == 8 * k); }
+bool res_encode_supported(uint32_t n, uint32_t k) { return (k == 512 || k == 1024) && nq_supported(n, k); }
 bool res_reconstruct_supported(uint32_t n, uint32_t k) { return res_encode_supported(n, k); }
 
 namespace {
@@ -462,13 +462,9 @@ static_assert(res_lds<256>(4) <= 40u * 1024u, "k = 256, n = 4k: four workgroups 
 template <int K>
 hipError_t launch_reconstruct_res_k(const DevTables& T, const ReconstructArgs& a, hipStream_t s) {
   using G = RGeo<K>;
-  const size_t nsyms = a.shard_len / 2;
-  if (nsyms == 0 || a.batch == 0) return hipSuccess;
-  if (nsyms > 0xffffffffu) return hipErrorInvalidValue;
-  const uint32_t tiles = static_cast<uint32_t>((nsyms + kRC - 1) / kRC);
-  const size_t blocks = a.batch * tiles;
-  if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
-  const uint32_t nb = static_cast<uint32_t>(blocks), ns = static_cast<uint32_t>(nsyms);
+  const TileGrid g = tile_grid(a.shard_len / 2, kRC, a.batch);
+  if (g.state != kGridOk) return grid_status(g);
+  const uint32_t nb = g.blocks, ns = g.count, tiles = g.tiles;
   k_reconstruct_res<K, 1><<<nb, G::kThreads, 0, s>>>(T, a, ns, tiles);
   if (a.n == 2u * K || a.trusted) k_reconstruct_res<K, 2><<<nb, G::kThreads, res_lds<K>(2), s>>>(T, a, ns, tiles);
   if (a.n == 4u * K) k_reconstruct_res<K, 4><<<nb, G::kThreads, res_lds<K>(4), s>>>(T, a, ns, tiles);
@@ -479,29 +475,16 @@ hipError_t launch_reconstruct_res_k(const DevTables& T, const ReconstructArgs& a
 template <int K>
 hipError_t launch_encode_res_k(const DevTables& T, const EncodeArgs& a, hipStream_t s) {
   using G = RGeo<K>;
-  const size_t nchunks = (a.payload_len + 2 * a.k - 1) / (2 * a.k);
-  if (nchunks == 0 || a.batch == 0) return hipSuccess;
-  if (nchunks > 0xffffffffu) return hipErrorInvalidValue;
-  const uint32_t tiles = static_cast<uint32_t>((nchunks + kRC - 1) / kRC);
-  const size_t blocks = a.batch * tiles;
-  if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
-  k_encode_res<K><<<static_cast<uint32_t>(blocks), G::kThreads, res_lds<K>(a.n / K), s>>>(T, a, static_cast<uint32_t>(nchunks), tiles);
+  const TileGrid g = tile_grid(encode_chunks(a), kRC, a.batch);
+  if (g.state != kGridOk) return grid_status(g);
+  k_encode_res<K><<<g.blocks, G::kThreads, res_lds<K>(a.n / K), s>>>(T, a, g.count, g.tiles);
   return hipGetLastError();
 }
 
 template <int K>
-hipError_t configure_res_k() {
-  hipError_t e = hipSuccess;
-  const void* enc = nullptr;  // (no K = 256 encode: the fast one serves it)
-  if constexpr (K != 256) enc = reinterpret_cast<const void*>(&k_encode_res<K>);
-  for (const void* f : {enc, reinterpret_cast<const void*>(&k_reconstruct_res<K, 2>),
-                        reinterpret_cast<const void*>(&k_reconstruct_res<K, 4>),
-                        reinterpret_cast<const void*>(&k_reconstruct_res<K, 8>)}) {
-    if (!f) continue;
-    const hipError_t r = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(res_lds<K>(8)));
-    if (r != hipSuccess && e == hipSuccess) e = r;
-  }
-  return e;
+void configure_res_k(LdsSetup& lds) {
+  if constexpr (K != 256) lds(&k_encode_res<K>, res_lds<K>(8));  // (no K = 256 encode: the fast one serves it)
+  each_k(NqList{}, [&](auto qc) { lds(&k_reconstruct_res<K, qc.value>, res_lds<K>(8)); });
 }
 }  // namespace
 
@@ -526,10 +509,11 @@ hipError_t launch_encode_res(const DevTables& T, const EncodeArgs& a, hipStream_
 }
 
 hipError_t configure_res_kernels() {
-  const hipError_t e = configure_res_k<1024>();
-  const hipError_t f = configure_res_k<512>();
-  const hipError_t g = configure_res_k<256>();
-  return e != hipSuccess ? e : f != hipSuccess ? f : g;
+  LdsSetup lds;
+  configure_res_k<1024>(lds);
+  configure_res_k<512>(lds);
+  configure_res_k<256>(lds);
+  return lds.err;
 }
 
 hipError_t bounds_take_res(uint32_t out[8]) { return bounds_take_tu(out); }

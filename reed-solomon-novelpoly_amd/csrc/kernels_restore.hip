@@ -2,7 +2,7 @@
 // small kernels around the encode that follows the reconstruct.
 //
 //  * k_restore_plan -- per payload, which rows the row-masked fast encode
-//    (kernels_fast.hip k_encode_masked) stores and which size-k segments hold
+//    (kernels_fast_planned.hip k_encode_masked) stores and which size-k segments hold
 //    one, as bit words that kernel reads with scalar loads: one pass over the
 //    n present flags per payload instead of one per column tile.
 //    k_verify_plan and k_recover_plan (below) are the same pass for the verify
@@ -164,7 +164,7 @@ hipError_t launch_copy_absent_rows(const uint8_t* src, size_t sstride, uint8_t* 
 // np_verify_shards_batch_dev (engine.cpp launch_recover): the same flow with
 // "present" in place of "absent" and a compare in place of the store.
 //
-//  * k_verify_plan -- the plan of kernels_fast.hip k_encode_verify: bit v set
+//  * k_verify_plan -- the plan of kernels_fast_planned.hip k_encode_verify: bit v set
 //    when row v is present, in [k, wanted_n), and the payload decoded.  Present
 //    systematic rows never differ from the re-encoding (the decode passes
 //    present data positions through), so the segment-0 bit is always clear.
@@ -305,7 +305,7 @@ hipError_t launch_verify_summary(const uint8_t* flags, const uint32_t* status, u
 
 // ------------------------------------------------------------ recover ----
 // np_recover_batch_dev with both the restore and the verify requested (engine.cpp
-// launch_recover): one plan for kernels_fast.hip k_encode_recover, which stores
+// launch_recover): one plan for kernels_fast_planned.hip k_encode_recover, which stores
 // the absent rows below wanted_n and compares the present ones in [k, wanted_n)
 // in one pass over the re-encoding.
 namespace {

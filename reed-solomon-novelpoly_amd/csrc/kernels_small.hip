@@ -7,7 +7,7 @@
 // Work mapping.  One wave owns a tile of 256 codeword columns and holds ALL K
 // positions of its lane's four columns in registers: Q[p] = the low / high
 // bytes of position p of columns 4l..4l+3 (the column-quad layout of
-// kernels_fast.hip with every position in one lane).  Every butterfly of a
+// kernels_fast_encode.hip with every position in one lane).  Every butterfly of a
 // size-K transform then pairs two registers of the same lane with a
 // wave-uniform multiplier: no LDS tile, no barrier, no cross-lane traffic.
 // Shard rows are position-major, so row p of the tile is register pair p:
@@ -19,7 +19,7 @@
 // Reference: additive FFT inc_afft.rs:139-214 (inverse) / :267-332 (forward);
 // encode inc_encode.rs:15-48 + mod.rs:117-157; reconstruct inc_reconstruct.rs:1-85
 // + mod.rs:162-239.  The decode folds the size-n inverse transform into
-// per-segment transforms exactly as kernels_fast.hip rec_segments (its
+// per-segment transforms exactly as kernels_fast_decode.hip rec_segments (its
 // derivation: the comment above rec_tiles there).
 #include "fast_common.hpp"
 
@@ -325,7 +325,7 @@ __global__ __launch_bounds__(256) void k_encode_small(DevTables T, EncodeArgs a,
 // ------------------------------------------------------------ reconstruct ----
 // Coefficient kappa_q (Cantor coordinates) of segment q in the first K
 // outputs' fold d = D_K(x0) ^ sum_q kappa_q x_q of a decode from nq segments
-// (kernels_fast.hip rec_segments / rec8_kappa; tests/test_oracle.py
+// (kernels_fast_decode.hip rec_segments / rec8_kappa; tests/test_oracle.py
 // test_rec8_kappa).
 __device__ __forceinline__ uint32_t small_kappa(int nq, int q) {
   if (nq == 2) return 1u;
@@ -334,7 +334,7 @@ __device__ __forceinline__ uint32_t small_kappa(int nq, int q) {
 }
 
 // One wave: 256 symbol columns of one payload.  The payload's record
-// (kernels_fast.hip k_prefix_locator / k_locator_records) gives nq' (0: fewer
+// (kernels_fast_records.hip k_prefix_locator / k_locator_records) gives nq' (0: fewer
 // than k present rows, skipped; 1: every systematic row present, copied; 2 or
 // NQ: decode from that many segments) and the premultiply (present rows) /
 // postmultiply (erased rows) tables of every row.
@@ -493,71 +493,43 @@ __global__ __launch_bounds__(256) void k_reconstruct_small(DevTables T, Reconstr
   }
 }
 
+// Four tiles per workgroup, numbered across the batch (tile_grid_packed).
 template <int K>
 hipError_t launch_encode_k(const DevTables& T, const EncodeArgs& a, hipStream_t s) {
-  const size_t nchunks = (a.payload_len + 2 * a.k - 1) / (2 * a.k);
-  if (nchunks == 0 || a.batch == 0) return hipSuccess;
-  if (nchunks > 0xffffffffu) return hipErrorInvalidValue;
-  const uint32_t tiles = static_cast<uint32_t>((nchunks + kTile - 1) / kTile);
-  const size_t blocks = (a.batch * tiles + 3) / 4;
-  if (a.batch * tiles > 0xffffffffu || blocks > 0x7fffffffu) return hipErrorInvalidValue;
-  k_encode_small<K><<<static_cast<uint32_t>(blocks), 256, 0, s>>>(T, a, static_cast<uint32_t>(nchunks), tiles);
+  const TileGrid g = tile_grid_packed(encode_chunks(a), kTile, a.batch, 4);
+  if (g.state != kGridOk) return grid_status(g);
+  k_encode_small<K><<<g.blocks, 256, 0, s>>>(T, a, g.count, g.tiles);
   return hipGetLastError();
 }
 
 template <int K, int NQ>
 hipError_t launch_reconstruct_k(const DevTables& T, const ReconstructArgs& a, hipStream_t s) {
-  const size_t nsyms = a.shard_len / 2;
-  if (nsyms == 0 || a.batch == 0) return hipSuccess;
-  if (nsyms > 0xffffffffu) return hipErrorInvalidValue;
-  const uint32_t tiles = static_cast<uint32_t>((nsyms + kTile - 1) / kTile);
-  const size_t blocks = (a.batch * tiles + 3) / 4;
-  if (a.batch * tiles > 0xffffffffu || blocks > 0x7fffffffu) return hipErrorInvalidValue;
-  k_reconstruct_small<K, NQ><<<static_cast<uint32_t>(blocks), 256, 0, s>>>(T, a, static_cast<uint32_t>(nsyms), tiles);
+  const TileGrid g = tile_grid_packed(a.shard_len / 2, kTile, a.batch, 4);
+  if (g.state != kGridOk) return grid_status(g);
+  k_reconstruct_small<K, NQ><<<g.blocks, 256, 0, s>>>(T, a, g.count, g.tiles);
   return hipGetLastError();
-}
-
-template <int K>
-hipError_t reconstruct_by_nq(const DevTables& T, const ReconstructArgs& a, hipStream_t s) {
-  if (a.n == 8u * K) return launch_reconstruct_k<K, 8>(T, a, s);
-  if (a.n == 4u * K) return launch_reconstruct_k<K, 4>(T, a, s);
-  return launch_reconstruct_k<K, 2>(T, a, s);
 }
 
 }  // namespace
 
+using SmallKs = Ints<1, 2, 4, 8, 16, 32>;
+
 bool small_encode_supported(uint32_t n, uint32_t k) {
-  return (k == 1 || k == 2 || k == 4 || k == 8 || k == 16 || k == 32) && n >= 2 * k &&
-         n <= kSmallMaxSeg * k;
+  return k_in(SmallKs{}, k) && n >= 2 * k && n <= kSmallMaxSeg * k;
 }
 
-bool small_reconstruct_supported(uint32_t n, uint32_t k) {
-  return (k == 1 || k == 2 || k == 4 || k == 8 || k == 16 || k == 32) &&
-         (n == 2 * k || n == 4 * k || n == 8 * k);
-}
+bool small_reconstruct_supported(uint32_t n, uint32_t k) { return k_in(SmallKs{}, k) && nq_supported(n, k); }
 
 hipError_t launch_encode_small(const DevTables& T, const EncodeArgs& a, hipStream_t s) {
-  switch (a.k) {
-    case 1: return launch_encode_k<1>(T, a, s);
-    case 2: return launch_encode_k<2>(T, a, s);
-    case 4: return launch_encode_k<4>(T, a, s);
-    case 8: return launch_encode_k<8>(T, a, s);
-    case 16: return launch_encode_k<16>(T, a, s);
-    case 32: return launch_encode_k<32>(T, a, s);
-    default: return hipErrorNotSupported;
-  }
+  return with_k(SmallKs{}, a.k, hipErrorNotSupported, [&](auto kc) { return launch_encode_k<kc.value>(T, a, s); });
 }
 
 hipError_t launch_reconstruct_small(const DevTables& T, const ReconstructArgs& a, hipStream_t s) {
-  switch (a.k) {
-    case 1: return reconstruct_by_nq<1>(T, a, s);
-    case 2: return reconstruct_by_nq<2>(T, a, s);
-    case 4: return reconstruct_by_nq<4>(T, a, s);
-    case 8: return reconstruct_by_nq<8>(T, a, s);
-    case 16: return reconstruct_by_nq<16>(T, a, s);
-    case 32: return reconstruct_by_nq<32>(T, a, s);
-    default: return hipErrorNotSupported;
-  }
+  return with_k(SmallKs{}, a.k, hipErrorNotSupported, [&](auto kc) {
+    constexpr int K = kc.value;
+    return with_nq(a.n, a.k, hipErrorNotSupported,
+                   [&](auto qc) { return launch_reconstruct_k<K, qc.value>(T, a, s); });
+  });
 }
 
 hipError_t bounds_take_small(uint32_t out[8]) { return bounds_take_tu(out); }

@@ -93,7 +93,8 @@ hipError_t launch_expand_rows(const uint8_t* src, const uint64_t* dst_off, uint8
 hipError_t launch_pack_rows(const uint8_t* src, const uint64_t* src_off, uint8_t* dst, size_t row_bytes, size_t nrows,
                             hipStream_t s);
 
-// ---- fast path (kernels_fast.hip) ----
+// ---- fast path (kernels_fast_encode.hip, kernels_fast_decode.hip; the records:
+// kernels_fast_records.hip) ----
 // Returns true if a specialised kernel serves (n, k).
 bool fast_encode_supported(uint32_t n, uint32_t k);
 bool fast_reconstruct_supported(uint32_t n, uint32_t k);
@@ -139,7 +140,10 @@ namespace np {
 // violation record of each instrumented translation unit since the last call
 // (out[0] = count), then cleared; hipErrorNotSupported in the product build.
 hipError_t bounds_take_generic(uint32_t out[8]);
-hipError_t bounds_take_fast(uint32_t out[8]);
+hipError_t bounds_take_fast_encode(uint32_t out[8]);
+hipError_t bounds_take_fast_planned(uint32_t out[8]);
+hipError_t bounds_take_fast_decode(uint32_t out[8]);
+hipError_t bounds_take_fast_records(uint32_t out[8]);
 hipError_t bounds_take_res(uint32_t out[8]);
 hipError_t bounds_take_small(uint32_t out[8]);
 hipError_t bounds_take_big(uint32_t out[8]);
@@ -147,7 +151,9 @@ hipError_t bounds_take_huge(uint32_t out[8]);
 
 // Raises the dynamic-LDS limit of the kernels that need > 64 KiB (call once per device).
 hipError_t configure_generic_kernels();
-hipError_t configure_fast_kernels();
+hipError_t configure_fast_encode_kernels();
+hipError_t configure_fast_planned_kernels();
+hipError_t configure_fast_decode_kernels();
 hipError_t configure_big_kernels();
 
 // ---- k = 1024 with the whole transform of a 64-column tile resident in the
@@ -185,7 +191,7 @@ hipError_t configure_huge_kernels();
 
 // ---- restoring absent shard rows (np_restore_shards_batch_dev) ----
 // Per-payload plan of the row-masked encode (kernels_restore.hip writes it,
-// kernels_fast.hip k_encode_masked reads it with scalar loads): first
+// kernels_fast_planned.hip k_encode_masked reads it with scalar loads): first
 // restore_seg_words(n, k) words with bit q set when rows [qk, (q+1)k) hold a row
 // to restore, then n / 32 words with bit v set when row v is one -- absent,
 // below wanted_n, and the payload's status (ReconstructArgs::status layout) OK.

@@ -49,7 +49,7 @@
 // Reference: inc_afft.rs:139-214 / :267-332 (transforms), inc_encode.rs:15-48
 // and mod.rs:117-157 (encode), inc_reconstruct.rs:1-113 and mod.rs:162-239
 // (reconstruct).  Decode algebra (the fold of the size-n transforms into
-// size-K ones, kappa, D_K): kernels_fast.hip, DESIGN.md §4.3.
+// size-K ones, kappa, D_K): kernels_fast_decode.hip, DESIGN.md §4.3.
 
 
 #include <algorithm>
@@ -775,7 +775,7 @@ __device__ __forceinline__ void rres_store_rows_pair(uint8_t* out0, uint8_t* out
 }
 
 // ----------------------------------------------------------- reconstruct ----
-// n = NQ * K, NQ in {2, 4, 8}.  As in k_reconstruct_fast (kernels_fast.hip,
+// n = NQ * K, NQ in {2, 4, 8}.  As in k_reconstruct_fast (kernels_fast_decode.hip,
 // DESIGN.md §4.3) the first k outputs are FFT(K, 0)(d) with
 //   NQ = 2: d = D(x0) ^ x0 ^ x1,   NQ = 4: d = D(x0) ^ x1 ^ x2 ^ beta (x2 ^ x3),
 //   NQ = 8: d = D(x0) ^ sum_q kappa_q x_q (rec8_kappa_res),
@@ -824,7 +824,7 @@ __device__ __forceinline__ void stage_row_tables(uint8_t* tile, const uint8_t* p
 // per wave: LDS byte M0 + 4 lane); the waves of the workgroup take the pieces
 // in turn.  The caller waits (s_waitcnt vmcnt) and synchronises before the
 // tables are read.  Written as asm (M0 set in the same statement,
-// kernels_fast.hip dma_tile), so the compiler adds no vmcnt(0) of its own.
+// kernels_fast_encode.hip dma_tile), so the compiler adds no vmcnt(0) of its own.
 __device__ __forceinline__ void dma_row_tables(uint8_t* tile, const uint8_t* pools, uint32_t row0, uint32_t nrows,
                                                uint32_t w, uint32_t lane, uint32_t nwaves) {
   static_assert(16 * kRowSlot == 5 * 256, "five 256-byte pieces per 16-row group");
@@ -993,7 +993,7 @@ __device__ __forceinline__ void res_copy_out(uint8_t* out_tile, const uint32_t (
   }
 }
 
-// NQ = 8: the fold coefficients of kernels_fast.hip rec8_kappa (Cantor
+// NQ = 8: the fold coefficients of kernels_fast_decode.hip rec8_kappa (Cantor
 // coordinates, all in GF(16); tests/test_oracle.py::test_rec8_kappa).
 __host__ __device__ constexpr uint32_t rec8_kappa_res(int q) {
   constexpr uint32_t k[8] = {1, 1, 3, 2, 12, 15, 10, 8};

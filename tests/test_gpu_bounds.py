@@ -50,16 +50,19 @@ def test_product_library_has_no_checks(gpu):
 
 
 @pytest.mark.skipif(not os.environ.get("NP_BOUNDS_CHILD"), reason="runs in the checked child process")
-def test_checker_catches_a_short_out_extent(gpu, monkeypatch):
+@pytest.mark.parametrize("wanted_n,k", [(2048, 1024), (1024, 256)], ids=["res-k1024", "fast-k256"])
+def test_checker_catches_a_short_out_extent(gpu, monkeypatch, wanted_n, k):
     """NP_BOUNDS_SELFTEST=64: the kernels see an out extent 64 bytes short, so
-    the copy-out of the last payload's last column must be flagged."""
+    the copy-out of the last payload's last column must be flagged: by the
+    resident decode (k = 1024, kernels_res.hip) and by the fast one (k = 256,
+    kernels_fast_decode.hip; each translation unit keeps its own record)."""
     import numpy as np
     import torch
 
     import novelpoly_amd as npa
     from novelpoly_amd import synth
 
-    p = npa.CodeParams.derive_parameters(2048, 1024)
+    p = npa.CodeParams.derive_parameters(wanted_n, k)
     n, k, sl, batch = p.n(), p.k(), 540, 2
     rows = torch.randint(0, 256, (batch, n, sl), dtype=torch.uint8, device="cuda")
     pres = torch.from_numpy(np.stack([synth.present_mask(b, n, 600) for b in range(batch)]).astype(np.uint8)).cuda()

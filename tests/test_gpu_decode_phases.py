@@ -1,5 +1,5 @@
 """The fast decode's phases between the transforms -- row issue, the layout
-exchanges' tile hand-off and the register copy-out (kernels_fast.hip
+exchanges' tile hand-off and the register copy-out (kernels_fast_decode.hip
 issue_rows_c, rec_segments, copy_out_cq) -- byte for byte against the oracle.
 
 Instances: NQ = n / k = 2, 4, 8 at K = 256 and NQ = 4 at K = 64 and 128 (they

@@ -1,5 +1,5 @@
 """The row-masked encodes of np_restore_shards_batch_dev and
-np_verify_shards_batch_dev (kernels_fast.hip k_encode_masked / k_encode_verify,
+np_verify_shards_batch_dev (kernels_fast_planned.hip k_encode_masked / k_encode_verify,
 fed by kernels_restore.hip k_restore_plan / k_verify_plan) over what their plan
 decides per payload: every set of marked size-k segments at n / k in {2, 4, 8},
 three shard lengths (a partial tile, a full plus a partial tile, the streaming

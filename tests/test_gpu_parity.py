@@ -544,7 +544,7 @@ def test_reconstruct_prefix_modes(gpu, oracle, nw, kw, plen):
                                         (2000, 667, 1024 * 33)])
 def test_reconstruct_empty_segments(gpu, oracle, nw, kw, plen):
     """Reconstruct skips the transforms of row blocks without a present row:
-    n = 8k fast path, k-row segments (record byte 1, kernels_fast.hip
+    n = 8k fast path, k-row segments (record byte 1, kernels_fast_records.hip
     segment_occupancy); k >= 512, 256-row sub-segments (kernels_big.hip
     k_big_records occupancy) and whole segments in the fold.  Whole segments
     erased inside wanted_n (alone, several, all but one), single 256-row blocks
@@ -602,7 +602,7 @@ def test_reconstruct_empty_segments(gpu, oracle, nw, kw, plen):
 def test_encode_multi_tile_workgroups(gpu, oracle, monkeypatch, nw, tpw, batch, stride_pad):
     """k = 256: one workgroup encodes `tpw` consecutive tiles of a payload and
     the next tile's payload arrives by LDS-DMA during the last shift
-    (kernels_fast.hip k_encode_multi; NP_ENC_TPW pins the tile count).  771
+    (kernels_fast_encode.hip k_encode_multi; NP_ENC_TPW pins the tile count).  771
     chunks = 3 full tiles and a partial one (loaded without DMA); wanted_n < n
     ends on an earlier shift; an odd payload stride takes the byte path; n = 8k
     runs shifts past the shared top-level products."""
@@ -633,7 +633,7 @@ def test_encode_multi_tile_workgroups(gpu, oracle, monkeypatch, nw, tpw, batch, 
                                               (700, 234, 4, 3)])
 def test_reconstruct_multi_tile_workgroups_small_k(gpu, oracle, monkeypatch, nw, kw, tpw, batch):
     """k = 64 / 128 (4 and 8 segments) over several tiles per payload with a
-    tile-count pin in the environment (one tile per workgroup there: kernels_fast.hip
+    tile-count pin in the environment (one tile per workgroup there: fast_family.hpp
     kMultiTile; round 4 measured multi-tile workgroups slower at these k).
     771 columns = 3 full tiles and one of 3 columns; random erasures, one
     payload with every systematic row present (copy mode), one with a single
@@ -675,7 +675,7 @@ def test_reconstruct_multi_tile_workgroups_small_k(gpu, oracle, monkeypatch, nw,
 @pytest.mark.parametrize("tpw,batch", [(2, 8), (3, 8), (4, 5), (8, 8)])
 def test_reconstruct_multi_tile_workgroups(gpu, oracle, monkeypatch, tpw, batch):
     """k = 256: one workgroup decodes `tpw` consecutive 256-column tiles of a
-    payload (kernels_fast.hip rec_tiles; NP_REC_TPW pins the count the launcher
+    payload (kernels_fast_decode.hip rec_tiles; NP_REC_TPW pins the count the launcher
     derives from the batch size).  771 symbol columns = 3 full tiles and one of
     3 columns, so workgroups end on partial tiles and on tile counts that tpw
     does not divide; every prefix mode, XCD-major and plain workgroup order."""
@@ -845,7 +845,7 @@ def test_host_pipeline_all_systematic_switched(gpu, env, nw, kw, plen):
 
 # Explicit parameters with n / k >= 16 (CodeParams::derive_parameters accepts
 # any k >= 1, mod.rs:43-61; encode(bytes, n) never derives them): the encode
-# runs the specialised kernels (k = 256: kernels_fast.hip; k = 512 / 1024:
+# runs the specialised kernels (k = 256: kernels_fast_*.hip; k = 512 / 1024:
 # kernels_big.hip, their only route there), the reconstruct the generic kernels.
 # k = 256 at n = 65536: the generic decode at the largest n behind the fast
 # encode.  (65536, 32768): above the sub-transform kernels' k <= 16384, the

@@ -1,4 +1,4 @@
-"""The recover encode of np_recover_batch_dev (kernels_fast.hip k_encode_recover
+"""The recover encode of np_recover_batch_dev (kernels_fast_planned.hip k_encode_recover
 with the RecoverRows sink, fed by kernels_restore.hip k_recover_plan) over what
 is new in it: the split of a wave's 16 rows into rows to store and rows to
 compare, a wanted_n anywhere from 0 to n with rows present at and above it,

@@ -285,7 +285,7 @@ def test_corrupted_row_beyond_prefix_changes_reference(oracle):
 
 def test_rec8_kappa(oracle):
     """The n = 8k decode folds the top inverse levels and the derivative's
-    single-bit terms into one coefficient per segment (kernels_fast.hip
+    single-bit terms into one coefficient per segment (kernels_fast_decode.hip
     rec8_kappa): d = D_K(x0) ^ sum_q kappa_q x_q equals the first K entries of
     formal_derivative(inverse_afft(a, n, 0)) (inc_reconstruct.rs:76-78) for
     random inputs; and the constants in the kernel source are these."""
@@ -295,7 +295,7 @@ def test_rec8_kappa(oracle):
     import numpy as np
 
     src = open(os.path.join(os.path.dirname(__file__), "..", "reed-solomon-novelpoly_amd", "csrc",
-                            "kernels_fast.hip")).read()
+                            "kernels_fast_decode.hip")).read()
     kappa = [int(v) for v in re.search(r"constexpr uint32_t k\[8\] = \{([^}]*)\}", src).group(1).split(",")]
     rng = np.random.default_rng(8)
     for K in (8, 16):

@@ -1,6 +1,6 @@
 """Experiment: per-wave phase timing of the multi-tile encode (config 3) from an
 NP_EXP=192 build (fast_common.hpp `stamp`: lane 0 of every wave writes
-s_memtime at each phase boundary of kernels_fast.hip encode_tile_multi /
+s_memtime at each phase boundary of kernels_fast_encode.hip encode_tile_multi /
 encode_shift, into the batch-stride padding past each payload's shard rows).
 For every phase: mean duration over waves and tiles, the slowest wave's, and
 the spread of arrival times.  GPU box:

@@ -1,5 +1,5 @@
 """Search a linear XOR swizzle f(column) for the fast kernels' LDS tile so that
-every access pattern of kernels_fast.hip is bank-conflict free (bank rules:
+every access pattern of kernels_fast_*.hip is bank-conflict free (bank rules:
 MI355X_MICROARCH.md §LDS).  Prints the matrix rows (one 5-bit mask per column bit)."""
 import random, sys
 

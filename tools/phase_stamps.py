@@ -21,7 +21,7 @@ s = torch.cuda.current_stream().cuda_stream
 sl = p.make_encoder(ctx).shard_len(plen)
 pay = torch.randint(0, 256, (b, plen), dtype=torch.uint8, device="cuda")
 # the stamped encode (NP_EXP bit 6) writes its own stamps past each payload's
-# rows (kernels_fast.hip encode_tile_multi: n shard_len + 4 KiB per tile)
+# rows (kernels_fast_encode.hip encode_tile_multi: n shard_len + 4 KiB per tile)
 enc_tiles = (plen // (2 * k) + 255) // 256 + 1
 bstride = n * sl + 4096 * enc_tiles
 sh = torch.zeros((b, bstride), dtype=torch.uint8, device="cuda")

@@ -1,5 +1,5 @@
 """Per-kernel register / spill summary of one HIP source file (gfx950):
-python tools/res_usage.py csrc/kernels_fast.hip [extra hipcc flags]."""
+python tools/res_usage.py csrc/kernels_fast_encode.hip [extra hipcc flags]."""
 import re
 import subprocess
 import sys
